@@ -23,6 +23,7 @@ import time
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # comm/compute overlap
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -53,7 +54,51 @@ def parse_args():
     p.add_argument("--graphs", type=str, default="auto",
                    choices=["auto", "on", "off"],
                    help="capture the whole step in a hipGraph (world==1)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last step "
+                        "computed (loss, logits, updated parameters; seeded "
+                        "samples where large) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present: a plain run already does "
+                        "only setup, warmup, the timed steps and the result "
+                        "line)")
     return p.parse_args()
+
+
+DUMP_LOGIT_ROWS = 64        # sampled (batch, position) rows of the logits
+DUMP_PER_PARAM = 16384      # sampled elements of each parameter tensor
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, logits: torch.Tensor,
+                 params: list) -> None:
+    """Write the last timed step's results as float32 .npy files. Large
+    arrays are sampled at fixed positions drawn from a seeded CPU generator,
+    so two builds run with the same arguments dump the same elements."""
+    gen = torch.Generator().manual_seed(4321)
+    rows = logits.detach().reshape(-1, logits.size(-1))
+    if rows.size(0) > DUMP_LOGIT_ROWS:
+        idx = torch.randint(0, rows.size(0), (DUMP_LOGIT_ROWS,), generator=gen)
+        rows = rows[idx.to(rows.device)]
+    chunks = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_PARAM:
+            idx = torch.randint(0, flat.numel(), (DUMP_PER_PARAM,),
+                                generator=gen)
+            flat = flat[idx.to(flat.device)]
+        chunks.append(flat.float().cpu())
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "logits": rows.float().cpu().numpy(),
+        "params": torch.cat(chunks).numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"dump of {total} bytes exceeds the cap"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def main() -> None:
@@ -134,13 +179,17 @@ def main() -> None:
     autocast = torch.autocast(device_type=device.type, dtype=amp_dtype,
                               enabled=True)
 
+    # what the last step returned to its caller, kept for --dump-outputs
+    keep_outputs = args.dump_outputs is not None and rank == 0
+    last = {}
+
     def eager_step(i: int) -> None:
         if state is not None:
             state.on_step(i)
         if bf16_master:
             for p in model_params:
                 p.grad = None
-            _, loss = train_mod(x, y)
+            logits, loss = train_mod(x, y)
             loss.backward()
             torch._foreach_copy_([m.grad for m in masters],
                                  [p.grad for p in model_params])
@@ -150,9 +199,11 @@ def main() -> None:
         else:
             opt.zero_grad(set_to_none=True)
             with autocast:
-                _, loss = train_mod(x, y)
+                logits, loss = train_mod(x, y)
             loss.backward()
             opt.step()
+        if keep_outputs:
+            last["logits"], last["loss"] = logits, loss
 
     step = eager_step
     use_graphs = want_graphs
@@ -174,7 +225,7 @@ def main() -> None:
                     for p in model_params:
                         if p.grad is not None:
                             p.grad.zero_()
-                    _, loss = train_mod(x, y)
+                    logits, loss = train_mod(x, y)
                     loss.backward()
                     torch._foreach_copy_([m.grad for m in masters],
                                          [p.grad for p in model_params])
@@ -185,7 +236,7 @@ def main() -> None:
                 opt.zero_grad(set_to_none=False)  # grads stay allocated
                 with torch.cuda.graph(g):
                     with autocast:
-                        _, loss = train_mod(x, y)
+                        logits, loss = train_mod(x, y)
                     loss.backward()
                     opt.step()
                     opt.zero_grad(set_to_none=False)
@@ -194,6 +245,8 @@ def main() -> None:
                 g.replay()
 
             step = graph_step
+            # the graph's static output tensors hold the last replay's values
+            last["logits"], last["loss"] = logits, loss
         except Exception as e:  # pragma: no cover - graph support varies
             print(f"# hipGraph capture unavailable ({e}); eager path",
                   file=sys.stderr)
@@ -226,6 +279,10 @@ def main() -> None:
     tokens = world * B * T * args.steps
     toks_per_s = tokens / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if keep_outputs:
+        dump_outputs(args.dump_outputs, last["loss"], last["logits"],
+                     list(model.parameters()))
 
     if rank == 0:
         out = {

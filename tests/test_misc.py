@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,8 +101,69 @@ def test_bench_help():
                           "--help"], capture_output=True, text=True,
                          timeout=120)
     assert res.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--precision", "--graphs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--precision", "--graphs",
+                 "--dump-outputs", "--full"):
         assert flag in res.stdout
+
+
+def _bench_tiny(out_dir, *extra):
+    import json
+
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+           "--steps", "2", "--warmup", "1", "--model", "tiny", "--batch", "2",
+           "--seq", "64", "--dump-outputs", str(out_dir), *extra]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
+                         cwd=REPO)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    return json.loads(lines[0])
+
+
+def _check_tiny_dump(out_dir):
+    import numpy as np
+
+    arrs = {n: np.load(os.path.join(out_dir, f"{n}.npy"))
+            for n in ("loss", "logits", "params")}
+    assert sorted(os.listdir(out_dir)) == ["logits.npy", "loss.npy",
+                                           "params.npy"]
+    for a in arrs.values():
+        assert a.dtype == np.float32
+        assert np.isfinite(a).all()
+    assert arrs["loss"].shape == (1,)
+    # random-init model, 2048-way softmax: loss stays near ln(2048) = 7.6
+    assert 5.0 < float(arrs["loss"][0]) < 10.0
+    assert arrs["logits"].shape == (64, 2048)  # 64 sampled rows x vocab
+    assert arrs["logits"].std() > 0
+    assert arrs["params"].ndim == 1 and arrs["params"].size > 16384
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    return arrs
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's loss/logits/parameters,
+    and the same arguments give the same arrays from run to run."""
+    import numpy as np
+
+    out = _bench_tiny(tmp_path / "a", "--device", "cpu")
+    assert out["steps"] == 2 and out["warmup"] == 1
+    assert out["ms_per_step"] > 0
+    assert abs(out["value"] - 2 * 64 / (out["ms_per_step"] / 1e3)) \
+        <= 1e-6 * out["value"]
+    a = _check_tiny_dump(str(tmp_path / "a"))
+    _bench_tiny(tmp_path / "b", "--device", "cpu", "--full")
+    b = _check_tiny_dump(str(tmp_path / "b"))
+    for name in a:
+        np.testing.assert_array_equal(a[name], b[name])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_gpu_graph(tmp_path):
+    """The whole-step hipGraph path dumps its static output tensors."""
+    out = _bench_tiny(tmp_path / "g")
+    assert out["config"]["hipgraph"] is True
+    assert out["steps"] == 2
+    _check_tiny_dump(str(tmp_path / "g"))
 
 
 def test_wait_time_csv_shape(tmp_path):

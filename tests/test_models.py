@@ -97,7 +97,10 @@ def test_template_scripts_2proc_cpu(script, extra):
     import random
 
     port = random.randint(20000, 40000)
-    env = dict(os.environ, ADAPCC_TRANSPORT="pg")
+    # a CPU/gloo run everywhere: hide any GPU from the two ranks (the
+    # templates pick RCCL when they see one, and RCCL needs a GPU per rank)
+    env = dict(os.environ, ADAPCC_TRANSPORT="pg", HIP_VISIBLE_DEVICES="-1",
+               CUDA_VISIBLE_DEVICES="-1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, script)] + extra
