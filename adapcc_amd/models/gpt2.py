@@ -53,21 +53,13 @@ class CausalSelfAttention(nn.Module):
         self.dropout = cfg.dropout
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        B, T, C = x.shape
-        qkv = self.c_attn(x)
-        q, k, v = qkv.split(C, dim=2)
-        hd = C // self.n_head
-        q = q.view(B, T, self.n_head, hd).transpose(1, 2)
-        k = k.view(B, T, self.n_head, hd).transpose(1, 2)
-        v = v.view(B, T, self.n_head, hd).transpose(1, 2)
-        from ..ops.attention import flash_attention
+        from ..ops import attention
 
-        y = flash_attention(
-            q, k, v, causal=True,
+        # packed [B,T,3C] in, [B,T,C] out: no split/transpose copies
+        return self.c_proj(attention.flash_attention_qkv(
+            self.c_attn(x), self.n_head,
             dropout_p=self.dropout if self.training else 0.0,
-        )
-        y = y.transpose(1, 2).contiguous().view(B, T, C)
-        return self.c_proj(y)
+        ))
 
 
 class MLP(nn.Module):

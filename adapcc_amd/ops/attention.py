@@ -4,7 +4,8 @@ Supported fast path: bf16, head_dim 64, causal, seq len a multiple of 128,
 no dropout. Anything else falls back to torch SDPA. Tensors are [B, H, S, D]
 with any batch/head/row strides (rows must be contiguous and 16-B aligned),
 so the usual ``.view(B,T,H,hd).transpose(1,2)`` projection views work
-without a copy.
+without a copy. ``flash_attention_qkv`` takes the packed [B,T,3C] projection
+and returns [B,T,C], reading and writing both layouts in place.
 """
 
 from __future__ import annotations
@@ -15,7 +16,8 @@ import torch
 
 from .fused import _core
 
-__all__ = ["flash_attention", "fa_supported"]
+__all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
+           "fa_qkv_supported"]
 
 
 def _strides3(t: torch.Tensor):
@@ -47,40 +49,92 @@ def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return bool(_core())
 
 
+def _launch_fwd(q, k, v, o, lse, scale):
+    B, H, S, _ = q.shape
+    strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                   lse.data_ptr(), B, H, S, strides, scale, stream)
+
+
+def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale):
+    """dq/dk/dv are written in place; delta = rowsum(dO*O) is computed by
+    the dq kernel into a workspace the dkv kernel then reads."""
+    B, H, S, _ = q.shape
+    # e.g. y.sum().backward() hands down an expanded, zero-stride dout
+    do = dout if _row_ok(dout) else dout.contiguous()
+    delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    strides = (_strides3(q) + _strides3(k) + _strides3(v) + _strides3(o) +
+               _strides3(do) + _strides3(dq) + _strides3(dk) +
+               _strides3(dv))
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _core().fa_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                   do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                   dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
+                   strides, scale, stream)
+
+
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
-        c = _core()
         B, H, S, D = q.shape
-        o = torch.empty((B, H, S, D), dtype=q.dtype, device=q.device)
+        # O lives in [B,S,H,D] memory so the caller's
+        # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
+        o = torch.empty((B, S, H, D), dtype=q.dtype,
+                        device=q.device).transpose(1, 2)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        c.fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                 lse.data_ptr(), B, H, S, strides, scale, stream)
+        _launch_fwd(q, k, v, o, lse, scale)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, dout):
-        c = _core()
         q, k, v, o, lse = ctx.saved_tensors
         B, H, S, D = q.shape
-        do = dout.contiguous()
-        delta = (do.float() * o.float()).sum(-1)  # [B,H,S] fp32
         dq = torch.empty((B, H, S, D), dtype=q.dtype, device=q.device)
         dk = torch.empty_like(dq)
         dv = torch.empty_like(dq)
-        strides = (_strides3(q) + _strides3(k) + _strides3(v) +
-                   _strides3(do) + _strides3(dq) + _strides3(dk) +
-                   _strides3(dv))
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        c.fa_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-                 lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
-                 dk.data_ptr(), dv.data_ptr(), B, H, S, strides, ctx.scale,
-                 stream)
+        _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale)
         return dq, dk, dv, None
+
+
+def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
+    """[B,T,C] (any row stride) -> its [B,H,T,C/H] view."""
+    B, T, C = t.shape
+    return t.view(B, T, n_head, C // n_head).transpose(1, 2)
+
+
+class _FlashAttnQkvFn(torch.autograd.Function):
+    """Attention straight off the packed projection: q, k, v are strided
+    views of qkv [B,T,3C], O is written as [B,T,C], and the backward writes
+    dq, dk, dv into the three thirds of one [B,T,3C] gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_head, scale):
+        B, T, C3 = qkv.shape
+        C = C3 // 3
+        q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+        y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B, n_head, T), dtype=torch.float32,
+                          device=qkv.device)
+        _launch_fwd(q, k, v, _heads(y, n_head), lse, scale)
+        ctx.save_for_backward(qkv, y, lse)
+        ctx.n_head = n_head
+        ctx.scale = scale
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        qkv, y, lse = ctx.saved_tensors
+        H = ctx.n_head
+        C = y.shape[2]
+        q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
+        _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
+                    ctx.scale)
+        return dqkv, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -93,3 +147,42 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         return _FlashAttnFn.apply(q, k, v, s)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
+
+
+def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
+                            dropout_p: float = 0.0) -> torch.Tensor:
+    """split -> head views -> flash_attention -> [B,T,C]."""
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+    y = flash_attention(q, k, v, causal=True, dropout_p=dropout_p)
+    return y.transpose(1, 2).contiguous().view(B, T, C)
+
+
+def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
+                     dropout_p: float) -> bool:
+    if dropout_p != 0.0:
+        return False
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3):
+        return False
+    B, T, C3 = qkv.shape
+    if C3 % (3 * n_head) != 0 or C3 // (3 * n_head) != 64:
+        return False
+    if T % 128 != 0 or T < 128 or B < 1:
+        return False
+    if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
+        return False
+    return bool(_core())
+
+
+def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
+                        dropout_p: float = 0.0) -> torch.Tensor:
+    """Causal self-attention on the packed projection qkv [B,T,3C] (q, k, v
+    thirds, heads contiguous within each); returns [B,T,C]. The qualifying
+    case (bf16, head_dim 64, T a multiple of 128, contiguous, no dropout)
+    runs the CDNA4 kernels directly on the packed layout with no copies;
+    anything else composes ``flash_attention`` from views."""
+    if fa_qkv_supported(qkv, n_head, dropout_p):
+        scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
+        return _FlashAttnQkvFn.apply(qkv, n_head, scale)
+    return _attention_qkv_composed(qkv, n_head, dropout_p)

@@ -352,21 +352,51 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 //   dP^T = V·dO^T         (A=V row frags, B=dO^T frags)
 //   dS^T = P^T * (dP^T - D[q]) * scale
 //   dQ^T += K^T·dS^T      (A=K^T tr frags, B=packed dS^T)
+//
+// The prologue also forms D[q] = rowsum(dO*O) from the dO fragments it holds
+// anyway plus one read of O, and stores it to p.delta for the dkv kernel.
 // ---------------------------------------------------------------------------
 struct FaBwdParams {
   const __bf16* q;
   const __bf16* k;
   const __bf16* v;
+  const __bf16* o;
   const __bf16* dout;
   const float* lse;      // [B,H,S]
-  const float* delta;    // [B,H,S] rowsum(dO*O)
+  float* delta;          // [B,H,S] rowsum(dO*O): written by the dq kernel,
+                         // read by the dkv kernel launched after it
   __bf16* dq;
   __bf16* dk;
   __bf16* dv;
-  TStride qs, ks, vs, dos_, dqs, dks, dvs;
+  TStride qs, ks, vs, os, dos_, dqs, dks, dvs;
   int H, S;
   float scale;
 };
+
+// Sum of the 8 bf16 products a[e]*b[e] in f32 (each product is exact),
+// added as a balanced tree over adjacent elements:
+// ((p0+p1)+(p2+p3)) + ((p4+p5)+(p6+p7)). The row sum is kept in this fixed
+// pairwise order end to end (see the dq prologue): it is the order of the
+// fp32 row reduction this replaces, so delta, and with it every gradient,
+// keeps its bits.
+__device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
+  union {
+    bf16x8 f;
+    unsigned u[4];
+  } x, y;
+  x.f = a;
+  y.f = b;
+  float pr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    // (+0 + p_even) + p_odd, one rounding: the element pair of word i
+    const float ev = __builtin_fmaf(__uint_as_float(x.u[i] << 16),
+                                    __uint_as_float(y.u[i] << 16), 0.f);
+    pr[i] = __builtin_fmaf(__uint_as_float(x.u[i] & 0xffff0000u),
+                           __uint_as_float(y.u[i] & 0xffff0000u), ev);
+  }
+  return (pr[0] + pr[1]) + (pr[2] + pr[3]);
+}
 
 __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
   // 64-row KV tiles: K and V row images, double-buffered (2 x 8 KB each).
@@ -385,21 +415,34 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
   const __bf16* kg = p.k + (long)b * p.ks.sb + (long)h * p.ks.sh;
   const __bf16* vg = p.v + (long)b * p.vs.sb + (long)h * p.vs.sh;
   const __bf16* dog = p.dout + (long)b * p.dos_.sb + (long)h * p.dos_.sh;
+  const __bf16* og = p.o + (long)b * p.os.sb + (long)h * p.os.sh;
   __bf16* dqg = p.dq + (long)b * p.dqs.sb + (long)h * p.dqs.sh;
 
   const int qb = qt * kQT + wave * 32;
   const int qrow = qb + (lane & 31);
 
+  // this lane holds 32 of its q row's 64 dO (and O) elements as four runs
+  // of 8 (columns c*16 + hi*8 ..); lane^32 holds the runs in between. n16[c]
+  // joins each run with its neighbour from the partner lane, so both lanes
+  // walk the same adjacent-pair tree over the whole row.
   bf16x8 qf[4], dof[4];
+  float n16[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    qf[c] = *reinterpret_cast<const bf16x8*>(
-        qg + (long)qrow * p.qs.ss + c * 16 + hi * 8);
     dof[c] = *reinterpret_cast<const bf16x8*>(
         dog + (long)qrow * p.dos_.ss + c * 16 + hi * 8);
+    const float n8 = dot8_tree(
+        dof[c], *reinterpret_cast<const bf16x8*>(
+                    og + (long)qrow * p.os.ss + c * 16 + hi * 8));
+    n16[c] = n8 + __shfl_xor(n8, 32, 64);
   }
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    qf[c] = *reinterpret_cast<const bf16x8*>(
+        qg + (long)qrow * p.qs.ss + c * 16 + hi * 8);
   const float lse2 = p.lse[(long)bh * p.S + qrow] * kLog2e;
-  const float dvq = p.delta[(long)bh * p.S + qrow];
+  const float dvq = (n16[0] + n16[1]) + (n16[2] + n16[3]);
+  if (hi == 0) p.delta[(long)bh * p.S + qrow] = dvq;
   const float c1 = p.scale * kLog2e;
 
   f32x16 dacc0 = {}, dacc1 = {};
@@ -814,15 +857,18 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
   hipLaunchKernelGGL(fa_fwd_kernel, grid, dim3(256), 0, stream, p);
 }
 
-void fa_backward(const void* q, const void* k, const void* v, const void* do_,
-                 const float* lse, const float* delta, void* dq, void* dk,
-                 void* dv, int B, int H, int S, const long* strides,
+// strides: q, k, v, o, dO, dq, dk, dv (3 each). delta is a [B,H,S] f32
+// workspace the dq kernel fills and the dkv kernel consumes.
+void fa_backward(const void* q, const void* k, const void* v, const void* o,
+                 const void* do_, const float* lse, float* delta, void* dq,
+                 void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream) {
   if (S % kQT != 0) throw std::runtime_error("fa_backward: S % 128 != 0");
   FaBwdParams p;
   p.q = (const __bf16*)q;
   p.k = (const __bf16*)k;
   p.v = (const __bf16*)v;
+  p.o = (const __bf16*)o;
   p.dout = (const __bf16*)do_;
   p.lse = lse;
   p.delta = delta;
@@ -832,10 +878,11 @@ void fa_backward(const void* q, const void* k, const void* v, const void* do_,
   p.qs = {strides[0], strides[1], strides[2]};
   p.ks = {strides[3], strides[4], strides[5]};
   p.vs = {strides[6], strides[7], strides[8]};
-  p.dos_ = {strides[9], strides[10], strides[11]};
-  p.dqs = {strides[12], strides[13], strides[14]};
-  p.dks = {strides[15], strides[16], strides[17]};
-  p.dvs = {strides[18], strides[19], strides[20]};
+  p.os = {strides[9], strides[10], strides[11]};
+  p.dos_ = {strides[12], strides[13], strides[14]};
+  p.dqs = {strides[15], strides[16], strides[17]};
+  p.dks = {strides[18], strides[19], strides[20]};
+  p.dvs = {strides[21], strides[22], strides[23]};
   p.H = H;
   p.S = S;
   p.scale = scale;

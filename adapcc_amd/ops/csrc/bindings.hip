@@ -89,9 +89,9 @@ void ce_backward(int dtype, const void* logits, const void* targets,
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream);
-void fa_backward(const void* q, const void* k, const void* v, const void* do_,
-                 const float* lse, const float* delta, void* dq, void* dk,
-                 void* dv, int B, int H, int S, const long* strides,
+void fa_backward(const void* q, const void* k, const void* v, const void* o,
+                 const void* do_, const float* lse, float* delta, void* dq,
+                 void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
@@ -193,17 +193,17 @@ PYBIND11_MODULE(_core, m) {
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
   m.def("fa_bwd",
-        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t dout,
+        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, int B, int H, int S, const std::vector<long>& strides,
            float scale, uintptr_t stream) {
-          if (strides.size() != 21)
-            throw std::runtime_error("fa_bwd: need 21 strides");
+          if (strides.size() != 24)
+            throw std::runtime_error("fa_bwd: need 24 strides");
           adapcc::fa_backward((const void*)q, (const void*)k, (const void*)v,
-                              (const void*)dout, (const float*)lse,
-                              (const float*)delta, (void*)dq, (void*)dk,
-                              (void*)dv, B, H, S, strides.data(), scale,
-                              reinterpret_cast<hipStream_t>(stream));
+                              (const void*)o, (const void*)dout,
+                              (const float*)lse, (float*)delta, (void*)dq,
+                              (void*)dk, (void*)dv, B, H, S, strides.data(),
+                              scale, reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });

@@ -58,6 +58,33 @@ def main():
         ms = bench(fb)
         print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
 
+    layer_path(B, H, S, D, fwd_flops, bwd_flops)
+
+
+def layer_path(B, H, S, D, fwd_flops, bwd_flops):
+    """What one transformer layer pays: packed projection [B,T,3C] in,
+    [B,T,C] out, contiguous [B,T,C] upstream gradient. 'composed' is
+    split + head views + flash_attention + transpose/contiguous (autograd
+    cats the three gradients); 'packed' is flash_attention_qkv."""
+    from adapcc_amd.ops.attention import (_attention_qkv_composed,
+                                          flash_attention_qkv)
+
+    C = H * D
+    qkv = torch.randn(B, S, 3 * C, device="cuda", dtype=torch.bfloat16,
+                      requires_grad=True)
+    gy = torch.randn(B, S, C, device="cuda", dtype=torch.bfloat16)
+    for name, f in (("layer composed", _attention_qkv_composed),
+                    ("layer packed", flash_attention_qkv)):
+        ms = bench(lambda: f(qkv, H))
+        print(f"{name} fwd:  {ms:7.3f} ms  {fwd_flops/ms/1e9:8.1f} TF/s")
+
+        def fb():
+            qkv.grad = None
+            f(qkv, H).backward(gy)
+
+        ms = bench(fb)
+        print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
+
 
 if __name__ == "__main__":
     main()
