@@ -7,8 +7,8 @@ from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
+from ..ops import attention
 from ..ops.fused import FusedLayerNorm
 
 
@@ -45,15 +45,12 @@ class EncoderBlock(nn.Module):
         )
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        B, T, C = x.shape
         h = self.ln1(x)
-        q, k, v = self.qkv(h).split(C, dim=2)
-        hd = C // self.heads
-        q = q.view(B, T, self.heads, hd).transpose(1, 2)
-        k = k.view(B, T, self.heads, hd).transpose(1, 2)
-        v = v.view(B, T, self.heads, hd).transpose(1, 2)
-        a = F.scaled_dot_product_attention(q, k, v)
-        a = a.transpose(1, 2).contiguous().view(B, T, C)
+        # bf16 with head_dim 64 on the GPU runs the non-causal flash
+        # attention kernels on the packed projection; anything else composes
+        # to SDPA on its head views
+        a = attention.flash_attention_qkv(self.qkv(h), self.heads,
+                                          causal=False)
         x = x + self.proj(a)
         x = x + self.mlp(self.ln2(x))
         return x

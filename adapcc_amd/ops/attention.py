@@ -1,11 +1,13 @@
 """Hand-written CDNA4 flash attention (csrc/attn.hip) with autograd.
 
-Supported fast path: bf16, head_dim 64, causal, seq len a multiple of 128,
-no dropout. Anything else falls back to torch SDPA. Tensors are [B, H, S, D]
-with any batch/head/row strides (rows must be contiguous and 16-B aligned),
-so the usual ``.view(B,T,H,hd).transpose(1,2)`` projection views work
-without a copy. ``flash_attention_qkv`` takes the packed [B,T,3C] projection
-and returns [B,T,C], reading and writing both layouts in place.
+Supported fast paths, both bf16, head_dim 64, self-attention (q, k, v of one
+shape), no dropout: causal with seq len a multiple of 128 (GPT-2), and
+non-causal with any seq len >= 1 (ViT: 197). Anything else falls back to
+torch SDPA. Tensors are [B, H, S, D] with any batch/head/row strides (rows
+must be contiguous and 16-B aligned), so the usual
+``.view(B,T,H,hd).transpose(1,2)`` projection views work without a copy.
+``flash_attention_qkv`` takes the packed [B,T,3C] projection and returns
+[B,T,C], reading and writing both layouts in place, in either mode.
 """
 
 from __future__ import annotations
@@ -35,35 +37,40 @@ def _row_ok(t: torch.Tensor) -> bool:
 
 def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                  causal: bool, dropout_p: float) -> bool:
-    if not (causal and dropout_p == 0.0):
+    if dropout_p != 0.0:
         return False
     if not (q.is_cuda and q.dtype == torch.bfloat16):
         return False
     if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
         return False
     B, H, S, D = q.shape
-    if D != 64 or S % 128 != 0 or S < 128:
+    if D != 64 or S < 1:
+        return False
+    if causal and S % 128 != 0:
         return False
     if not (_row_ok(q) and _row_ok(k) and _row_ok(v)):
         return False
     return bool(_core())
 
 
-def _launch_fwd(q, k, v, o, lse, scale):
+def _launch_fwd(q, k, v, o, lse, scale, causal=True):
     B, H, S, _ = q.shape
     strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                   lse.data_ptr(), B, H, S, strides, scale, stream)
+                   lse.data_ptr(), B, H, S, strides, scale, stream, causal)
 
 
-def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale):
+def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
+                delta=None):
     """dq/dk/dv are written in place; delta = rowsum(dO*O) is computed by
-    the dq kernel into a workspace the dkv kernel then reads."""
+    the dq kernel into a workspace (``delta``: contiguous [B,H,S] fp32, made
+    here when not given) the dkv kernel then reads."""
     B, H, S, _ = q.shape
     # e.g. y.sum().backward() hands down an expanded, zero-stride dout
     do = dout if _row_ok(dout) else dout.contiguous()
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    if delta is None:
+        delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     strides = (_strides3(q) + _strides3(k) + _strides3(v) + _strides3(o) +
                _strides3(do) + _strides3(dq) + _strides3(dk) +
                _strides3(dv))
@@ -71,32 +78,61 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale):
     _core().fa_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
-                   strides, scale, stream)
+                   strides, scale, stream, causal)
+
+
+def _fa_forward_lse(q, k, v, scale, causal):
+    """Forward only: (o, lse), lse the [B,H,S] fp32 natural-log logsumexp
+    of the scaled scores."""
+    B, H, S, D = q.shape
+    # O lives in [B,S,H,D] memory so the caller's
+    # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
+    o = torch.empty((B, S, H, D), dtype=q.dtype,
+                    device=q.device).transpose(1, 2)
+    lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    _launch_fwd(q, k, v, o, lse, scale, causal=causal)
+    return o, lse
+
+
+def _fa_fn_forward(ctx, q, k, v, scale, causal):
+    o, lse = _fa_forward_lse(q, k, v, scale, causal)
+    ctx.save_for_backward(q, k, v, o, lse)
+    ctx.scale = scale
+    return o
+
+
+def _fa_fn_backward(ctx, dout, causal):
+    q, k, v, o, lse = ctx.saved_tensors
+    B, H, S, D = q.shape
+    dq = torch.empty((B, H, S, D), dtype=q.dtype, device=q.device)
+    dk = torch.empty_like(dq)
+    dv = torch.empty_like(dq)
+    _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale, causal=causal)
+    return dq, dk, dv, None
 
 
 class _FlashAttnFn(torch.autograd.Function):
+    """Causal, S % 128 == 0."""
+
     @staticmethod
     def forward(ctx, q, k, v, scale):
-        B, H, S, D = q.shape
-        # O lives in [B,S,H,D] memory so the caller's
-        # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
-        o = torch.empty((B, S, H, D), dtype=q.dtype,
-                        device=q.device).transpose(1, 2)
-        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        _launch_fwd(q, k, v, o, lse, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.scale = scale
-        return o
+        return _fa_fn_forward(ctx, q, k, v, scale, True)
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o, lse = ctx.saved_tensors
-        B, H, S, D = q.shape
-        dq = torch.empty((B, H, S, D), dtype=q.dtype, device=q.device)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
-        _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale)
-        return dq, dk, dv, None
+        return _fa_fn_backward(ctx, dout, True)
+
+
+class _FlashAttnNoncausalFn(torch.autograd.Function):
+    """Non-causal self-attention, any S >= 1."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        return _fa_fn_forward(ctx, q, k, v, scale, False)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _fa_fn_backward(ctx, dout, False)
 
 
 def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
@@ -105,36 +141,56 @@ def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
     return t.view(B, T, n_head, C // n_head).transpose(1, 2)
 
 
+def _fa_qkv_fn_forward(ctx, qkv, n_head, scale, causal):
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+    y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, n_head, T), dtype=torch.float32,
+                      device=qkv.device)
+    _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal)
+    ctx.save_for_backward(qkv, y, lse)
+    ctx.n_head = n_head
+    ctx.scale = scale
+    return y
+
+
+def _fa_qkv_fn_backward(ctx, dy, causal):
+    qkv, y, lse = ctx.saved_tensors
+    H = ctx.n_head
+    C = y.shape[2]
+    q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
+    _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
+                ctx.scale, causal=causal)
+    return dqkv, None, None
+
+
 class _FlashAttnQkvFn(torch.autograd.Function):
     """Attention straight off the packed projection: q, k, v are strided
     views of qkv [B,T,3C], O is written as [B,T,C], and the backward writes
-    dq, dk, dv into the three thirds of one [B,T,3C] gradient."""
+    dq, dk, dv into the three thirds of one [B,T,3C] gradient. Causal."""
 
     @staticmethod
     def forward(ctx, qkv, n_head, scale):
-        B, T, C3 = qkv.shape
-        C = C3 // 3
-        q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
-        y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty((B, n_head, T), dtype=torch.float32,
-                          device=qkv.device)
-        _launch_fwd(q, k, v, _heads(y, n_head), lse, scale)
-        ctx.save_for_backward(qkv, y, lse)
-        ctx.n_head = n_head
-        ctx.scale = scale
-        return y
+        return _fa_qkv_fn_forward(ctx, qkv, n_head, scale, True)
 
     @staticmethod
     def backward(ctx, dy):
-        qkv, y, lse = ctx.saved_tensors
-        H = ctx.n_head
-        C = y.shape[2]
-        q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
-        _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
-                    ctx.scale)
-        return dqkv, None, None
+        return _fa_qkv_fn_backward(ctx, dy, True)
+
+
+class _FlashAttnQkvNoncausalFn(torch.autograd.Function):
+    """The same on the packed projection, non-causal, any T >= 1."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_head, scale):
+        return _fa_qkv_fn_forward(ctx, qkv, n_head, scale, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _fa_qkv_fn_backward(ctx, dy, False)
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -144,23 +200,25 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     kernels when the shape qualifies, torch SDPA otherwise."""
     if fa_supported(q, k, v, causal, dropout_p):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        return _FlashAttnFn.apply(q, k, v, s)
+        fn = _FlashAttnFn if causal else _FlashAttnNoncausalFn
+        return fn.apply(q, k, v, s)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
 
 
 def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
-                            dropout_p: float = 0.0) -> torch.Tensor:
+                            dropout_p: float = 0.0,
+                            causal: bool = True) -> torch.Tensor:
     """split -> head views -> flash_attention -> [B,T,C]."""
     B, T, C3 = qkv.shape
     C = C3 // 3
     q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
-    y = flash_attention(q, k, v, causal=True, dropout_p=dropout_p)
+    y = flash_attention(q, k, v, causal=causal, dropout_p=dropout_p)
     return y.transpose(1, 2).contiguous().view(B, T, C)
 
 
 def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
-                     dropout_p: float) -> bool:
+                     dropout_p: float, causal: bool = True) -> bool:
     if dropout_p != 0.0:
         return False
     if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3):
@@ -168,7 +226,7 @@ def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
     B, T, C3 = qkv.shape
     if C3 % (3 * n_head) != 0 or C3 // (3 * n_head) != 64:
         return False
-    if T % 128 != 0 or T < 128 or B < 1:
+    if T < 1 or B < 1 or (causal and T % 128 != 0):
         return False
     if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
         return False
@@ -176,13 +234,16 @@ def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
 
 
 def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
-                        dropout_p: float = 0.0) -> torch.Tensor:
-    """Causal self-attention on the packed projection qkv [B,T,3C] (q, k, v
+                        dropout_p: float = 0.0,
+                        causal: bool = True) -> torch.Tensor:
+    """Self-attention on the packed projection qkv [B,T,3C] (q, k, v
     thirds, heads contiguous within each); returns [B,T,C]. The qualifying
-    case (bf16, head_dim 64, T a multiple of 128, contiguous, no dropout)
-    runs the CDNA4 kernels directly on the packed layout with no copies;
-    anything else composes ``flash_attention`` from views."""
-    if fa_qkv_supported(qkv, n_head, dropout_p):
+    case (bf16, head_dim 64, contiguous, no dropout; T a multiple of 128 when
+    causal, any T >= 1 when not) runs the CDNA4 kernels directly on the
+    packed layout with no copies; anything else composes
+    ``flash_attention`` from views."""
+    if fa_qkv_supported(qkv, n_head, dropout_p, causal):
         scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
-        return _FlashAttnQkvFn.apply(qkv, n_head, scale)
-    return _attention_qkv_composed(qkv, n_head, dropout_p)
+        fn = _FlashAttnQkvFn if causal else _FlashAttnQkvNoncausalFn
+        return fn.apply(qkv, n_head, scale)
+    return _attention_qkv_composed(qkv, n_head, dropout_p, causal)

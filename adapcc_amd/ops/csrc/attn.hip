@@ -1,4 +1,6 @@
-// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim=64, causal.
+// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim=64, in two
+// modes: causal with S % 128 == 0 (GPT-2), and non-causal self-attention
+// over any S >= 1 (ViT: S = 197).
 //
 // Replaces the stock SDPA path for the GPT-2 flagship workload, where the
 // aotriton kernels ran at ~2% of the MFMA roof (rocprof round-1 evidence:
@@ -21,6 +23,15 @@
 // state and the O accumulator stay indexed by the SAME lane-local q; the
 // backward splits FA2-style into a dq kernel (q-tile outer) and a dkv
 // kernel (kv-tile outer), both recomputing P from the saved logsumexp.
+//
+// The three kernels are templates on <kCausal, kRagged>. <true,false> is
+// the GPT-2 case. The non-causal mode loops over all ceil(S/64) tiles;
+// its kRagged form (S % 128 != 0) clamps the row index of every load to
+// S-1 (so no byte at a row >= S is read and whatever lands in a padding
+// position is finite), masks keys >= S to kNegBig before the running max
+// (P forced to 0 in the backward), predicates every store on row < S, and
+// skips the MFMA/softmax work of 32-row half-tiles and of waves that are
+// all padding (those waves still stage and take every barrier).
 //
 // Reference parity note: the reference (JoeyYoung/adapcc) has no attention
 // kernels (models used stock torch); this op exists to meet BASELINE.json's
@@ -158,12 +169,29 @@ struct FaParams {
   float scale;
 };
 
+// Row index used for a load: in the ragged mode rows >= S do not exist, so
+// they read row S-1 instead (real data, hence finite).
+// Two spellings, chosen per kernel by what the register allocator makes of
+// them: the forward keeps 64-bit row arithmetic (its causal code is then
+// instruction for instruction the earlier one), the backward kernels index
+// in 32 bits, which keeps all their instantiations free of scratch.
+template <bool kRagged>
+__device__ __forceinline__ long ld_row(long row, int S) {
+  return kRagged ? (long)min((int)row, S - 1) : row;
+}
+template <bool kRagged>
+__device__ __forceinline__ int ld_row32(int row, int S) {
+  return kRagged ? min(row, S - 1) : row;
+}
+
 // ---------------------------------------------------------------------------
 // Forward.
-// Grid: (S/128, B*H); block 256 = 4 waves, wave w owns q rows
+// Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
 // qt*128 + w*32 .. +31.
 // ---------------------------------------------------------------------------
+template <bool kCausal, bool kRagged>
 __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
+  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
   // 64-row KV tiles, double-buffered: [64][64] bf16 images as two 32-row
   // halves (row_img_byte addresses within each half).
   __shared__ __attribute__((aligned(16))) char smem[4 * 8192];
@@ -185,6 +213,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   const int qb = qt * kQT + wave * 32;      // this wave's first q row
   const int qrow = qb + (lane & 31);        // this lane's q row
+  const long qld = ld_row<kRagged>((long)qrow, p.S);
 
   // Q^T B-fragments, direct from global: lane l holds
   // Q[qrow][chunk*16 + 8*hi + e].
@@ -192,7 +221,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(
-        qg + (long)qrow * p.qs.ss + c * 16 + hi * 8);
+        qg + qld * p.qs.ss + c * 16 + hi * 8);
 
   f32x16 acc0 = {}, acc1 = {};
   float m = kNegBig, ssum = 0.f;
@@ -206,20 +235,21 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   const int srow = threadIdx.x >> 3;        // staging: this thread's row
   const int scol = (threadIdx.x & 7) * 8;   // and column (bf16)
-  const int n64 = (qt + 1) * (kQT / 64);    // causal: 64-row tiles
+  // 64-row tiles: up to the diagonal (causal) or all of them
+  const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
 
   // prologue: stage tile 0 (rows srow and srow+32 of K and V)
   {
+    const long r0 = ld_row<kRagged>((long)srow, p.S);
+    const long r1 = ld_row<kRagged>((long)(srow + 32), p.S);
     *reinterpret_cast<uint4*>(kimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + (long)srow * p.ks.ss + scol);
+        *reinterpret_cast<const uint4*>(kg + r0 * p.ks.ss + scol);
     *reinterpret_cast<uint4*>(kimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + (long)(srow + 32) * p.ks.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(kg + r1 * p.ks.ss + scol);
     *reinterpret_cast<uint4*>(vimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + (long)srow * p.vs.ss + scol);
+        *reinterpret_cast<const uint4*>(vg + r0 * p.vs.ss + scol);
     *reinterpret_cast<uint4*>(vimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + (long)(srow + 32) * p.vs.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(vg + r1 * p.vs.ss + scol);
   }
   __syncthreads();
 
@@ -229,17 +259,24 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
     uint4 nk0, nk1, nv0, nv1;
     const bool pref = t + 1 < n64;
     if (pref) {
-      const long kb0 = (long)(t + 1) * 64 + srow;
+      const long kb = (long)(t + 1) * 64 + srow;
+      const long kb0 = ld_row<kRagged>(kb, p.S);
+      const long kb1 = ld_row<kRagged>(kb + 32, p.S);
       nk0 = *reinterpret_cast<const uint4*>(kg + kb0 * p.ks.ss + scol);
-      nk1 = *reinterpret_cast<const uint4*>(kg + (kb0 + 32) * p.ks.ss + scol);
+      nk1 = *reinterpret_cast<const uint4*>(kg + kb1 * p.ks.ss + scol);
       nv0 = *reinterpret_cast<const uint4*>(vg + kb0 * p.vs.ss + scol);
-      nv1 = *reinterpret_cast<const uint4*>(vg + (kb0 + 32) * p.vs.ss + scol);
+      nv1 = *reinterpret_cast<const uint4*>(vg + kb1 * p.vs.ss + scol);
     }
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int kbase = t * 64 + half * 32;
-      if (kbase > qb + 31) break;  // wave-uniform causal cut
+      if (kCausal) {
+        if (kbase > qb + 31) break;  // wave-uniform causal cut
+      } else if (kRagged) {
+        // wave-uniform: a half-tile or a wave that is all padding
+        if (kbase >= p.S || qb >= p.S) break;
+      }
       const char* ki = kimg(cur) + half * 4096;
       const char* vi = vimg(cur) + half * 4096;
 
@@ -253,12 +290,13 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
       float pv[16];
       float tmax = kNegBig;
-      if (kbase + 31 > qb) {
-        // diagonal tile for this wave: apply the causal mask
+      if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
+        // diagonal tile for this wave: apply the causal mask; ragged: the
+        // tile that holds key S-1, mask the keys past it
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
-          pv[r] = (kglob > qrow) ? kNegBig : s[r];
+          pv[r] = (kCausal ? kglob > qrow : kglob >= p.S) ? kNegBig : s[r];
           tmax = fmaxf(tmax, pv[r]);
         }
       } else {
@@ -321,6 +359,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   // epilogue: combine row-sum halves, normalize, store O and lse
   const float stot = ssum + __shfl_xor(ssum, 32, 64);
   const float inv = 1.f / stot;
+  if (kRagged && qrow >= p.S) return;  // stores only; no barrier follows
   if ((lane >> 5) == 0)
     lseg[qrow] = p.scale * m + __builtin_amdgcn_logf(stot) * kLn2;
 
@@ -346,9 +385,9 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 #undef vimg
 
 // ---------------------------------------------------------------------------
-// Backward dQ. Grid (S/128, B*H). Per q-tile, loop kv tiles:
+// Backward dQ. Grid (ceil(S/128), B*H). Per q-tile, loop kv tiles:
 //   S^T = K·Q^T           (A=K row frags, B=Q^T frags)      lane-q local
-//   P^T = exp2(S*c1 - lse*log2e), causal-masked
+//   P^T = exp2(S*c1 - lse*log2e), masked (causal, or keys >= S)
 //   dP^T = V·dO^T         (A=V row frags, B=dO^T frags)
 //   dS^T = P^T * (dP^T - D[q]) * scale
 //   dQ^T += K^T·dS^T      (A=K^T tr frags, B=packed dS^T)
@@ -398,7 +437,9 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
   return (pr[0] + pr[1]) + (pr[2] + pr[3]);
 }
 
+template <bool kCausal, bool kRagged>
 __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
+  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
   // 64-row KV tiles: K and V row images, double-buffered (2 x 8 KB each).
   __shared__ __attribute__((aligned(16))) char smem[4 * 8192];
 #define kimg(i) (smem + (i) * 8192)
@@ -420,6 +461,7 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
 
   const int qb = qt * kQT + wave * 32;
   const int qrow = qb + (lane & 31);
+  const long qld = ld_row32<kRagged>(qrow, p.S);
 
   // this lane holds 32 of its q row's 64 dO (and O) elements as four runs
   // of 8 (columns c*16 + hi*8 ..); lane^32 holds the runs in between. n16[c]
@@ -430,37 +472,38 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     dof[c] = *reinterpret_cast<const bf16x8*>(
-        dog + (long)qrow * p.dos_.ss + c * 16 + hi * 8);
+        dog + qld * p.dos_.ss + c * 16 + hi * 8);
     const float n8 = dot8_tree(
         dof[c], *reinterpret_cast<const bf16x8*>(
-                    og + (long)qrow * p.os.ss + c * 16 + hi * 8));
+                    og + qld * p.os.ss + c * 16 + hi * 8));
     n16[c] = n8 + __shfl_xor(n8, 32, 64);
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(
-        qg + (long)qrow * p.qs.ss + c * 16 + hi * 8);
-  const float lse2 = p.lse[(long)bh * p.S + qrow] * kLog2e;
+        qg + qld * p.qs.ss + c * 16 + hi * 8);
+  const float lse2 = p.lse[(long)bh * p.S + qld] * kLog2e;
   const float dvq = (n16[0] + n16[1]) + (n16[2] + n16[3]);
-  if (hi == 0) p.delta[(long)bh * p.S + qrow] = dvq;
+  if (hi == 0 && (!kRagged || qrow < p.S))
+    p.delta[(long)bh * p.S + qrow] = dvq;
   const float c1 = p.scale * kLog2e;
 
   f32x16 dacc0 = {}, dacc1 = {};
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
-  const int n64 = (qt + 1) * (kQT / 64);
+  const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
   {
+    const long r0 = ld_row32<kRagged>(srow, p.S);
+    const long r1 = ld_row32<kRagged>(srow + 32, p.S);
     *reinterpret_cast<uint4*>(kimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + (long)srow * p.ks.ss + scol);
+        *reinterpret_cast<const uint4*>(kg + r0 * p.ks.ss + scol);
     *reinterpret_cast<uint4*>(kimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + (long)(srow + 32) * p.ks.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(kg + r1 * p.ks.ss + scol);
     *reinterpret_cast<uint4*>(vimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + (long)srow * p.vs.ss + scol);
+        *reinterpret_cast<const uint4*>(vg + r0 * p.vs.ss + scol);
     *reinterpret_cast<uint4*>(vimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + (long)(srow + 32) * p.vs.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(vg + r1 * p.vs.ss + scol);
   }
   __syncthreads();
 
@@ -469,17 +512,22 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
     uint4 nk0, nk1, nv0, nv1;
     const bool pref = t + 1 < n64;
     if (pref) {
-      const long kb0 = (long)(t + 1) * 64 + srow;
+      const long kb0 = ld_row32<kRagged>((t + 1) * 64 + srow, p.S);
+      const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, p.S);
       nk0 = *reinterpret_cast<const uint4*>(kg + kb0 * p.ks.ss + scol);
-      nk1 = *reinterpret_cast<const uint4*>(kg + (kb0 + 32) * p.ks.ss + scol);
+      nk1 = *reinterpret_cast<const uint4*>(kg + kb1 * p.ks.ss + scol);
       nv0 = *reinterpret_cast<const uint4*>(vg + kb0 * p.vs.ss + scol);
-      nv1 = *reinterpret_cast<const uint4*>(vg + (kb0 + 32) * p.vs.ss + scol);
+      nv1 = *reinterpret_cast<const uint4*>(vg + kb1 * p.vs.ss + scol);
     }
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int kbase = t * 64 + half * 32;
-      if (kbase > qb + 31) break;
+      if (kCausal) {
+        if (kbase > qb + 31) break;
+      } else if (kRagged) {
+        if (kbase >= p.S || qb >= p.S) break;  // all padding
+      }
       const char* ki = kimg(cur) + half * 4096;
       const char* vi = vimg(cur) + half * 4096;
 
@@ -493,12 +541,12 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
       __builtin_amdgcn_s_setprio(0);
 
       float ds[16];
-      if (kbase + 31 > qb) {
+      if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
           const float pe =
-              (kglob > qrow)
+              (kCausal ? kglob > qrow : kglob >= p.S)
                   ? 0.f
                   : __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lse2));
           ds[r] = pe * (dp[r] - dvq) * p.scale;
@@ -535,6 +583,7 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
     cur ^= 1;
   }
 
+  if (kRagged && qrow >= p.S) return;  // stores only; no barrier follows
   __bf16* drow = dqg + (long)qrow * p.dqs.ss;
 #pragma unroll
   for (int db = 0; db < 2; ++db) {
@@ -558,15 +607,17 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
 
 
 // ---------------------------------------------------------------------------
-// Backward dK/dV. Grid (S/128, B*H); wave owns kv rows kt*128+w*32..+31,
-// loops q tiles >= the diagonal:
+// Backward dK/dV. Grid (ceil(S/128), B*H); wave owns kv rows kt*128+w*32..+31,
+// loops q tiles >= the diagonal (causal) or all q tiles:
 //   S = Q·K^T   as C[q][k]: A=Q row frags (LDS), B=K direct (registers)
 //   P^T[k][q] = exp2(S*c1 - lse[q]*log2e) masked            lane-k local
 //   dP[q][k]: A=dO row frags, B=V^T direct (registers)
 //   dV += P^T·dO   (A=packed P^T, B=dO^T tr frags)
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
+template <bool kCausal, bool kRagged>
 __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
+  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
   // 64-row q tiles: Q and dO row images, double-buffered (2 x 8 KB each),
   // plus lse/delta broadcast tiles; the epilogue reuses [0,32K) as
   // per-wave f32 scratch for the coalesced dV/dK stores.
@@ -594,6 +645,7 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
 
   const int kbb = kt * kQT + wave * 32;     // this wave's first k row
   const int krow = kbb + (lane & 31);       // this lane's k row
+  const long kld = ld_row32<kRagged>(krow, p.S);
 
   // K and V^T B-fragments direct from global: lane holds
   // K[krow][chunk*16+8*hi+e] / V[krow][...]
@@ -601,9 +653,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     kf[c] = *reinterpret_cast<const bf16x8*>(
-        kg + (long)krow * p.ks.ss + c * 16 + hi * 8);
+        kg + kld * p.ks.ss + c * 16 + hi * 8);
     vf[c] = *reinterpret_cast<const bf16x8*>(
-        vg + (long)krow * p.vs.ss + c * 16 + hi * 8);
+        vg + kld * p.vs.ss + c * 16 + hi * 8);
   }
 
   const float c1 = p.scale * kLog2e;
@@ -611,25 +663,26 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
-  const int t0 = kt;                        // first 64-row q tile (diagonal)
-  const int n64 = p.S / 64;
+  const int t0 = kCausal ? kt : 0;          // first 64-row q tile
+  const int n64 = (p.S + 63) / 64;
 
   // stage q/dO tile t0 (rows t0*64 + srow, + srow+32)
   {
-    const long qb0 = (long)t0 * 64;
+    const int qb0 = t0 * 64;
+    const long r0 = ld_row32<kRagged>(qb0 + srow, p.S);
+    const long r1 = ld_row32<kRagged>(qb0 + srow + 32, p.S);
     *reinterpret_cast<uint4*>(qimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(qg + (qb0 + srow) * p.qs.ss + scol);
+        *reinterpret_cast<const uint4*>(qg + r0 * p.qs.ss + scol);
     *reinterpret_cast<uint4*>(qimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(qg + (qb0 + srow + 32) * p.qs.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(qg + r1 * p.qs.ss + scol);
     *reinterpret_cast<uint4*>(doimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(dog + (qb0 + srow) * p.dos_.ss + scol);
+        *reinterpret_cast<const uint4*>(dog + r0 * p.dos_.ss + scol);
     *reinterpret_cast<uint4*>(doimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(dog + (qb0 + srow + 32) * p.dos_.ss +
-                                        scol);
+        *reinterpret_cast<const uint4*>(dog + r1 * p.dos_.ss + scol);
     if (threadIdx.x < 64) {
-      lsetile[threadIdx.x] = lseg[qb0 + threadIdx.x] * kLog2e;
-      dtile[threadIdx.x] = deltag[qb0 + threadIdx.x];
+      const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, p.S);
+      lsetile[threadIdx.x] = lseg[rq] * kLog2e;
+      dtile[threadIdx.x] = deltag[rq];
     }
   }
   __syncthreads();
@@ -640,25 +693,29 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
     float nlse = 0.f, ndel = 0.f;
     const bool pref = t + 1 < n64;
     if (pref) {
-      const long qb1 = (long)(t + 1) * 64;
-      nq0 = *reinterpret_cast<const uint4*>(qg + (qb1 + srow) * p.qs.ss +
-                                            scol);
-      nq1 = *reinterpret_cast<const uint4*>(qg + (qb1 + srow + 32) * p.qs.ss +
-                                            scol);
-      nd0 = *reinterpret_cast<const uint4*>(dog + (qb1 + srow) * p.dos_.ss +
-                                            scol);
-      nd1 = *reinterpret_cast<const uint4*>(
-          dog + (qb1 + srow + 32) * p.dos_.ss + scol);
+      const int qb1 = (t + 1) * 64;
+      const long r0 = ld_row32<kRagged>(qb1 + srow, p.S);
+      const long r1 = ld_row32<kRagged>(qb1 + srow + 32, p.S);
+      nq0 = *reinterpret_cast<const uint4*>(qg + r0 * p.qs.ss + scol);
+      nq1 = *reinterpret_cast<const uint4*>(qg + r1 * p.qs.ss + scol);
+      nd0 = *reinterpret_cast<const uint4*>(dog + r0 * p.dos_.ss + scol);
+      nd1 = *reinterpret_cast<const uint4*>(dog + r1 * p.dos_.ss + scol);
       if (threadIdx.x < 64) {
-        nlse = lseg[qb1 + threadIdx.x] * kLog2e;
-        ndel = deltag[qb1 + threadIdx.x];
+        const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, p.S);
+        nlse = lseg[rq] * kLog2e;
+        ndel = deltag[rq];
       }
     }
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int qbase = t * 64 + half * 32;
-      if (qbase + 31 < kbb) continue;       // wave-uniform causal cut
+      if (kCausal) {
+        if (qbase + 31 < kbb) continue;     // wave-uniform causal cut
+      } else if (kRagged) {
+        // wave-uniform: a q half-tile or a k-row wave that is all padding
+        if (qbase >= p.S || kbb >= p.S) break;
+      }
       const char* qi = qimg(cur) + half * 4096;
       const char* di = doimg(cur) + half * 4096;
       const float* lsec = lsetile + (cur ? 64 : 0) + half * 32;
@@ -674,13 +731,13 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
       __builtin_amdgcn_s_setprio(0);
 
       float pv[16], ds[16];
-      if (qbase < kbb + 31) {
-        // diagonal: mask q < k
+      if (kCausal ? qbase < kbb + 31 : kRagged && qbase + 31 >= p.S) {
+        // diagonal: mask q < k; ragged: mask the q rows past S-1
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qglob = qbase + crow(r, hi);
           const float pe =
-              (qglob < krow)
+              (kCausal ? qglob < krow : qglob >= p.S)
                   ? 0.f
                   : __builtin_amdgcn_exp2f(
                         __builtin_fmaf(sacc[r], c1, -lsec[crow(r, hi)]));
@@ -759,8 +816,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
           : "=&v"(lo), "=&v"(hi2)
           : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]));
       uint2 st = {lo, hi2};
-      *reinterpret_cast<uint2*>(outg + (long)(kbb + row) * os.ss + dhalf +
-                                mq * 4) = st;
+      if (!kRagged || kbb + row < p.S)
+        *reinterpret_cast<uint2*>(outg + (long)(kbb + row) * os.ss + dhalf +
+                                  mq * 4) = st;
     }
     __syncthreads();  // scratch reused for dK after dV drains
   }
@@ -838,8 +896,10 @@ __global__ void mfma_probe_kernel(const __bf16* a, const __bf16* b, float* c) {
 // ---------------------------------------------------------------------------
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
-                float scale, hipStream_t stream) {
-  if (S % kQT != 0) throw std::runtime_error("fa_forward: S % 128 != 0");
+                float scale, hipStream_t stream, bool causal) {
+  if (S < 1) throw std::runtime_error("fa_forward: S < 1");
+  if (causal && S % kQT != 0)
+    throw std::runtime_error("fa_forward: causal needs S % 128 == 0");
   FaParams p;
   p.q = (const __bf16*)q;
   p.k = (const __bf16*)k;
@@ -853,8 +913,16 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
   p.H = H;
   p.S = S;
   p.scale = scale;
-  dim3 grid(S / kQT, B * H);
-  hipLaunchKernelGGL(fa_fwd_kernel, grid, dim3(256), 0, stream, p);
+  dim3 grid((S + kQT - 1) / kQT, B * H);
+  if (causal)
+    hipLaunchKernelGGL((fa_fwd_kernel<true, false>), grid, dim3(256), 0,
+                       stream, p);
+  else if (S % kQT == 0)
+    hipLaunchKernelGGL((fa_fwd_kernel<false, false>), grid, dim3(256), 0,
+                       stream, p);
+  else
+    hipLaunchKernelGGL((fa_fwd_kernel<false, true>), grid, dim3(256), 0,
+                       stream, p);
 }
 
 // strides: q, k, v, o, dO, dq, dk, dv (3 each). delta is a [B,H,S] f32
@@ -862,8 +930,10 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
-                 float scale, hipStream_t stream) {
-  if (S % kQT != 0) throw std::runtime_error("fa_backward: S % 128 != 0");
+                 float scale, hipStream_t stream, bool causal) {
+  if (S < 1) throw std::runtime_error("fa_backward: S < 1");
+  if (causal && S % kQT != 0)
+    throw std::runtime_error("fa_backward: causal needs S % 128 == 0");
   FaBwdParams p;
   p.q = (const __bf16*)q;
   p.k = (const __bf16*)k;
@@ -886,9 +956,23 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
   p.H = H;
   p.S = S;
   p.scale = scale;
-  dim3 grid(S / kQT, B * H);
-  hipLaunchKernelGGL(fa_bwd_dq_kernel, grid, dim3(256), 0, stream, p);
-  hipLaunchKernelGGL(fa_bwd_dkv_kernel, grid, dim3(256), 0, stream, p);
+  dim3 grid((S + kQT - 1) / kQT, B * H);
+  if (causal) {
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, false>), grid, dim3(256), 0,
+                       stream, p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<true, false>), grid, dim3(256), 0,
+                       stream, p);
+  } else if (S % kQT == 0) {
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false>), grid, dim3(256), 0,
+                       stream, p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<false, false>), grid, dim3(256), 0,
+                       stream, p);
+  } else {
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, true>), grid, dim3(256), 0,
+                       stream, p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<false, true>), grid, dim3(256), 0,
+                       stream, p);
+  }
 }
 
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream) {

@@ -1,7 +1,11 @@
 """Flash-attention kernel timing: hand-written CDNA4 kernels vs torch SDPA.
 
-Run on a GPU box:  python benchmarks/attn_bench.py
+Run on a GPU box:  python benchmarks/attn_bench.py [--shape gpt2|vit]
+
+gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
+(ViT-base at 224 px).
 """
+import argparse
 import math
 import os
 import sys
@@ -10,6 +14,12 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {
+    # name: (B, H, S, D, causal)
+    "gpt2": (64, 12, 1024, 64, True),
+    "vit": (64, 12, 197, 64, False),
+}
 
 
 def bench(fn, iters=20, warmup=5):
@@ -24,9 +34,17 @@ def bench(fn, iters=20, warmup=5):
 
 
 def main():
-    from adapcc_amd.ops.attention import _FlashAttnFn
+    from adapcc_amd.ops.attention import fa_supported, flash_attention
 
-    B, H, S, D = 64, 12, 1024, 64  # GPT-2 small flagship shape
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", choices=sorted(SHAPES), default="gpt2")
+    ap.add_argument("--iters", type=int, default=None,
+                    help="timed calls per figure (default 20; 200 for vit, "
+                         "whose calls are ~10x shorter)")
+    args = ap.parse_args()
+    B, H, S, D, causal = SHAPES[args.shape]
+    iters = args.iters or (200 if args.shape == "vit" else 20)
+
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)
     q = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16,
@@ -34,20 +52,22 @@ def main():
     k = torch.randn_like(q, requires_grad=True)
     v = torch.randn_like(q, requires_grad=True)
     g = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
+    # a missing kernel is an error here, not a silent SDPA-vs-SDPA run
+    assert fa_supported(q, k, v, causal, 0.0)
 
-    # FLOPs (causal): fwd 2 matmuls, bwd 5
-    fwd_flops = 4 * B * H * S * S * D / 2
+    # FLOPs: fwd 2 matmuls, bwd 5; the causal mask halves both
+    fwd_flops = 4 * B * H * S * S * D / (2 if causal else 1)
     bwd_flops = 2.5 * fwd_flops
 
     def fa_fwd():
-        return _FlashAttnFn.apply(q, k, v, scale)
+        return flash_attention(q, k, v, causal=causal, scale=scale)
 
     def sdpa_fwd():
         return torch.nn.functional.scaled_dot_product_attention(
-            q, k, v, is_causal=True)
+            q, k, v, is_causal=causal)
 
     for name, f in (("adapcc-fa", fa_fwd), ("torch-sdpa", sdpa_fwd)):
-        ms = bench(lambda: f())
+        ms = bench(lambda: f(), iters)
         print(f"{name} fwd:  {ms:7.3f} ms  {fwd_flops/ms/1e9:8.1f} TF/s")
 
         def fb():
@@ -55,13 +75,13 @@ def main():
             o = f()
             o.backward(g)
 
-        ms = bench(fb)
+        ms = bench(fb, iters)
         print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
 
-    layer_path(B, H, S, D, fwd_flops, bwd_flops)
+    layer_path(B, H, S, D, causal, fwd_flops, bwd_flops, iters)
 
 
-def layer_path(B, H, S, D, fwd_flops, bwd_flops):
+def layer_path(B, H, S, D, causal, fwd_flops, bwd_flops, iters):
     """What one transformer layer pays: packed projection [B,T,3C] in,
     [B,T,C] out, contiguous [B,T,C] upstream gradient. 'composed' is
     split + head views + flash_attention + transpose/contiguous (autograd
@@ -75,14 +95,14 @@ def layer_path(B, H, S, D, fwd_flops, bwd_flops):
     gy = torch.randn(B, S, C, device="cuda", dtype=torch.bfloat16)
     for name, f in (("layer composed", _attention_qkv_composed),
                     ("layer packed", flash_attention_qkv)):
-        ms = bench(lambda: f(qkv, H))
+        ms = bench(lambda: f(qkv, H, causal=causal), iters)
         print(f"{name} fwd:  {ms:7.3f} ms  {fwd_flops/ms/1e9:8.1f} TF/s")
 
         def fb():
             qkv.grad = None
-            f(qkv, H).backward(gy)
+            f(qkv, H, causal=causal).backward(gy)
 
-        ms = bench(fb)
+        ms = bench(fb, iters)
         print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
 
 

@@ -24,6 +24,9 @@ def main():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--batch", type=int, default=32)
     p.add_argument("--tiny", action="store_true")
+    p.add_argument("--bf16", action="store_true",
+                   help="forward and loss under autocast bf16 (reaches the "
+                        "flash attention kernels)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -63,7 +66,9 @@ def main():
         if state is not None:
             state.on_step(step)
         opt.zero_grad(set_to_none=True)
-        loss = crit(model(x), y)
+        with torch.autocast("cuda", torch.bfloat16,
+                            enabled=args.bf16 and use_cuda):
+            loss = crit(model(x), y)
         loss.backward()
         opt.step()
         if use_cuda:
