@@ -35,22 +35,24 @@ def _row_ok(t: torch.Tensor) -> bool:
     return all(s % 8 == 0 for s in _strides3(t))
 
 
+def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
+               dropout_p: float) -> bool:
+    """What the kernels take, layout aside: bf16 on the GPU, head_dim 64,
+    S >= 1 (a multiple of 128 when causal), no dropout, extension built."""
+    if dropout_p != 0.0 or not (t.is_cuda and t.dtype == torch.bfloat16):
+        return False
+    if D != 64 or S < 1 or (causal and S % 128 != 0):
+        return False
+    return bool(_core())
+
+
 def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                  causal: bool, dropout_p: float) -> bool:
-    if dropout_p != 0.0:
-        return False
-    if not (q.is_cuda and q.dtype == torch.bfloat16):
-        return False
     if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
-        return False
-    B, H, S, D = q.shape
-    if D != 64 or S < 1:
-        return False
-    if causal and S % 128 != 0:
         return False
     if not (_row_ok(q) and _row_ok(k) and _row_ok(v)):
         return False
-    return bool(_core())
+    return _kernel_ok(q, q.shape[3], q.shape[2], causal, dropout_p)
 
 
 def _launch_fwd(q, k, v, o, lse, scale, causal=True):
@@ -94,103 +96,62 @@ def _fa_forward_lse(q, k, v, scale, causal):
     return o, lse
 
 
-def _fa_fn_forward(ctx, q, k, v, scale, causal):
-    o, lse = _fa_forward_lse(q, k, v, scale, causal)
-    ctx.save_for_backward(q, k, v, o, lse)
-    ctx.scale = scale
-    return o
-
-
-def _fa_fn_backward(ctx, dout, causal):
-    q, k, v, o, lse = ctx.saved_tensors
-    B, H, S, D = q.shape
-    dq = torch.empty((B, H, S, D), dtype=q.dtype, device=q.device)
-    dk = torch.empty_like(dq)
-    dv = torch.empty_like(dq)
-    _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale, causal=causal)
-    return dq, dk, dv, None
-
-
-class _FlashAttnFn(torch.autograd.Function):
-    """Causal, S % 128 == 0."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, scale):
-        return _fa_fn_forward(ctx, q, k, v, scale, True)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _fa_fn_backward(ctx, dout, True)
-
-
-class _FlashAttnNoncausalFn(torch.autograd.Function):
-    """Non-causal self-attention, any S >= 1."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, scale):
-        return _fa_fn_forward(ctx, q, k, v, scale, False)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _fa_fn_backward(ctx, dout, False)
-
-
 def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
     """[B,T,C] (any row stride) -> its [B,H,T,C/H] view."""
     B, T, C = t.shape
     return t.view(B, T, n_head, C // n_head).transpose(1, 2)
 
 
-def _fa_qkv_fn_forward(ctx, qkv, n_head, scale, causal):
-    B, T, C3 = qkv.shape
-    C = C3 // 3
-    q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
-    y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B, n_head, T), dtype=torch.float32,
-                      device=qkv.device)
-    _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal)
-    ctx.save_for_backward(qkv, y, lse)
-    ctx.n_head = n_head
-    ctx.scale = scale
-    return y
+class _FlashAttnFn(torch.autograd.Function):
+    """[B,H,S,D] q, k, v; causal needs S % 128 == 0."""
 
+    @staticmethod
+    def forward(ctx, q, k, v, scale, causal):
+        o, lse = _fa_forward_lse(q, k, v, scale, causal)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale, ctx.causal = scale, causal
+        return o
 
-def _fa_qkv_fn_backward(ctx, dy, causal):
-    qkv, y, lse = ctx.saved_tensors
-    H = ctx.n_head
-    C = y.shape[2]
-    q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
-    dqkv = torch.empty_like(qkv)
-    dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
-    _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
-                ctx.scale, causal=causal)
-    return dqkv, None, None
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse = ctx.saved_tensors
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        dk = torch.empty_like(dq)
+        dv = torch.empty_like(dq)
+        _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale,
+                    causal=ctx.causal)
+        return dq, dk, dv, None, None
 
 
 class _FlashAttnQkvFn(torch.autograd.Function):
     """Attention straight off the packed projection: q, k, v are strided
     views of qkv [B,T,3C], O is written as [B,T,C], and the backward writes
-    dq, dk, dv into the three thirds of one [B,T,3C] gradient. Causal."""
+    dq, dk, dv into the three thirds of one [B,T,3C] gradient."""
 
     @staticmethod
-    def forward(ctx, qkv, n_head, scale):
-        return _fa_qkv_fn_forward(ctx, qkv, n_head, scale, True)
-
-    @staticmethod
-    def backward(ctx, dy):
-        return _fa_qkv_fn_backward(ctx, dy, True)
-
-
-class _FlashAttnQkvNoncausalFn(torch.autograd.Function):
-    """The same on the packed projection, non-causal, any T >= 1."""
-
-    @staticmethod
-    def forward(ctx, qkv, n_head, scale):
-        return _fa_qkv_fn_forward(ctx, qkv, n_head, scale, False)
+    def forward(ctx, qkv, n_head, scale, causal):
+        B, T, C3 = qkv.shape
+        C = C3 // 3
+        q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+        y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B, n_head, T), dtype=torch.float32,
+                          device=qkv.device)
+        _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal)
+        ctx.save_for_backward(qkv, y, lse)
+        ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
+        return y
 
     @staticmethod
     def backward(ctx, dy):
-        return _fa_qkv_fn_backward(ctx, dy, False)
+        qkv, y, lse = ctx.saved_tensors
+        H = ctx.n_head
+        C = y.shape[2]
+        q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
+        _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
+                    ctx.scale, causal=ctx.causal)
+        return dqkv, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -200,8 +161,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     kernels when the shape qualifies, torch SDPA otherwise."""
     if fa_supported(q, k, v, causal, dropout_p):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        fn = _FlashAttnFn if causal else _FlashAttnNoncausalFn
-        return fn.apply(q, k, v, s)
+        return _FlashAttnFn.apply(q, k, v, s, causal)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
 
@@ -219,18 +179,12 @@ def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
 
 def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
                      dropout_p: float, causal: bool = True) -> bool:
-    if dropout_p != 0.0:
-        return False
-    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3):
-        return False
-    B, T, C3 = qkv.shape
-    if C3 % (3 * n_head) != 0 or C3 // (3 * n_head) != 64:
-        return False
-    if T < 1 or B < 1 or (causal and T % 128 != 0):
+    if qkv.dim() != 3 or qkv.shape[0] < 1 or qkv.shape[2] % (3 * n_head):
         return False
     if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
         return False
-    return bool(_core())
+    return _kernel_ok(qkv, qkv.shape[2] // (3 * n_head), qkv.shape[1],
+                      causal, dropout_p)
 
 
 def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
@@ -244,6 +198,5 @@ def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
     ``flash_attention`` from views."""
     if fa_qkv_supported(qkv, n_head, dropout_p, causal):
         scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
-        fn = _FlashAttnQkvFn if causal else _FlashAttnQkvNoncausalFn
-        return fn.apply(qkv, n_head, scale)
+        return _FlashAttnQkvFn.apply(qkv, n_head, scale, causal)
     return _attention_qkv_composed(qkv, n_head, dropout_p, causal)

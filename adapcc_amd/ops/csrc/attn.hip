@@ -12,12 +12,7 @@
 // v_mfma_f32_32x32x16_bf16 so each lane owns one Q row's scores, online
 // softmax in the exp2 domain, and P redistributed to MFMA operand layout
 // with v_cvt_pk_bf16_f32 + v_permlane32_swap_b32 (no LDS round trip).
-//
-// Layout conventions for v_mfma_f32_32x32x16_bf16 (verified on hardware by
-// the mfma_probe test):
-//   A[32x16]: lane l holds A[i = l%32][k = 8*(l/32) + e], e = 0..7
-//   B[16x32]: lane l holds B[k = 8*(l/32) + e][j = l%32]
-//   C[32x32]: lane l holds C[(r&3) + 8*(r>>2) + 4*(l>>5)][l%32], r = 0..15
+// The MFMA fragment maps and the LDS row image are in attn_frag.h.
 //
 // Forward computes O^T = V^T · P^T per 32-wide KV tile so the online-max
 // state and the O accumulator stay indexed by the SAME lane-local q; the
@@ -37,136 +32,48 @@
 // kernels (models used stock torch); this op exists to meet BASELINE.json's
 // "hot ops as hand-written MFMA/LDS kernels" requirement.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+
+#include "attn_frag.h"
 
 namespace adapcc {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kQT = 128;    // q rows per workgroup (32 per wave)
 constexpr float kNegBig = -3.0e38f;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// C-tile row of accumulator register r for this lane-half (l>>5).
-__device__ __forceinline__ constexpr int crow(int r, int hi) {
-  return (r & 3) + 8 * (r >> 2) + 4 * hi;
-}
-
-// Redistribute 8 C-register f32 values (rows crow(o..o+7)) into one MFMA
-// operand fragment holding elements k = 8*(l>>5) + (0..7) of the SAME
-// lane-column: cvt_pk pairs then permlane32_swap exchanges the mismatched
-// quartets between lane halves (guide T12). The s_nop covers the
-// VALU-write -> v_permlane hazard window.
-__device__ __forceinline__ bf16x8 pack_frag(const float* p) {
-  unsigned a0, a1, b0, b1;
-  asm volatile(
-      "v_cvt_pk_bf16_f32 %0, %4, %5\n\t"
-      "v_cvt_pk_bf16_f32 %1, %6, %7\n\t"
-      "v_cvt_pk_bf16_f32 %2, %8, %9\n\t"
-      "v_cvt_pk_bf16_f32 %3, %10, %11\n\t"
-      "s_nop 1\n\t"
-      "v_permlane32_swap_b32 %0, %2\n\t"
-      "v_permlane32_swap_b32 %1, %3"
-      : "=&v"(a0), "=&v"(a1), "=&v"(b0), "=&v"(b1)
-      : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]),
-        "v"(p[6]), "v"(p[7]));
-  union {
-    unsigned u[4];
-    bf16x8 f;
-  } r;
-  r.u[0] = a0;
-  r.u[1] = a1;
-  r.u[2] = b0;
-  r.u[3] = b1;
-  return r.f;
-}
-
-// ---------------------------------------------------------------------------
-// LDS images.
-//
-// Row image (K / Q / dO as direct row-major fragments): [32][64] bf16 with
-// byte ^= ((row&7)<<4) XOR swizzle, read as 16-B ds_read_b128.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int row_img_byte(int row, int col_bf16) {
-  return (row * 128 + col_bf16 * 2) ^ ((row & 7) << 4);
-}
-
-// A-or-B fragment read from a row image: lane l takes row (l&31), 8
-// consecutive bf16 at column chunk*16 + (l>>5)*8.
-__device__ __forceinline__ bf16x8 read_row_frag(const char* img, int lane,
-                                                int chunk) {
-  const int byte = row_img_byte(lane & 31, chunk * 16 + (lane >> 5) * 8);
-  return *reinterpret_cast<const bf16x8*>(img + byte);
-}
-
-// Transpose fragments come straight from the SAME swizzled row image via
-// ds_read_b64_tr_b16. Measured instruction semantics (tr2 probe, gfx950):
-// within each 16-lane group, writing lane ids as 16g+4t+m (t,m in 0..3),
-// destination lane 16g+4t+m element j receives
-//     lds[ addr_supplied_by_lane(16g+4j+t) + m elements ]
-// (addresses 8-B aligned; each source lane names one 4-element chunk).
-// So lane s supplies the address of X[8*(s>>5) + 4r + ((s>>2)&3)]
-//                                   [db*32 + 16*((s>>4)&1) + 4*(s&3)]
-// and every lane l ends up with X[kb*16 + 8*(l>>5) + 4r + j][db*32 + (l&31)]
-// in element 4r+j -- exactly the MFMA operand fragment of X^T. The 4-elem
-// chunk is 8 B inside one 16-B slot, so the row image's XOR swizzle keeps
-// it contiguous and aligned.
-__device__ __forceinline__ int tr_addr_byte(int lane, int kb, int db, int r) {
-  const int row = kb * 16 + r * 4 + 8 * (lane >> 5) + ((lane >> 2) & 3);
-  const int col = db * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-  return row_img_byte(row, col);
-}
-
-// Two tr reads -> one 8-element fragment: lane l holds X[8*(l>>5)+e][l&31]
-// for k in [kb*16,+16), d in [db*32,+32), X^T-fragment oriented.
-__device__ __forceinline__ bf16x8 read_tr_frag(const char* img, int lane,
-                                               int kb, int db) {
-  typedef __attribute__((address_space(3))) bf16x4 lds_v4;
-  union {
-    bf16x4 h[2];
-    bf16x8 f;
-  } r;
-  r.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_v4*)(img + tr_addr_byte(lane, kb, db, 0)));
-  r.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_v4*)(img + tr_addr_byte(lane, kb, db, 1)));
-  return r.f;
-}
-
-// ---------------------------------------------------------------------------
-// Staging: 256 threads cooperatively copy a [32][64] bf16 tile (4 KB) from
-// global (row stride `rs` elements) into an LDS image. One 16-B load + one
-// 16-B ds_write per thread.
-// ---------------------------------------------------------------------------
-
 // Strides for one tensor: plane = b*sb + h*sh, row stride ss (elements).
 struct TStride {
   long sb, sh, ss;
 };
 
+// Base of the (b, h) plane of a tensor.
+template <typename T>
+__device__ __forceinline__ T* plane(T* x, const TStride& s, int b, int h) {
+  return x + (long)b * s.sb + (long)h * s.sh;
+}
+
+// One parameter block for all three kernels; the forward fills and reads
+// only the first part.
 struct FaParams {
-  const __bf16* q;
-  const __bf16* k;
-  const __bf16* v;
-  __bf16* o;
+  const __bf16 *q, *k, *v;
+  __bf16* o;           // written by the forward, read by the dq kernel
   float* lse;          // [B,H,S] natural-log row logsumexp
   TStride qs, ks, vs, os;
   int H, S;
   float scale;
+  // backward only
+  const __bf16* dout;
+  float* delta;        // [B,H,S] rowsum(dO*O): written by the dq kernel,
+                       // read by the dkv kernel launched after it
+  __bf16 *dq, *dk, *dv;
+  TStride dos_, dqs, dks, dvs;
 };
 
 // Row index used for a load: in the ragged mode rows >= S do not exist, so
@@ -185,6 +92,89 @@ __device__ __forceinline__ int ld_row32(int row, int S) {
 }
 
 // ---------------------------------------------------------------------------
+// Staging: 256 threads cooperatively copy a [64][64] bf16 tile (8 KB) from
+// global (row stride `ss` elements) into an LDS image of two 32-row halves
+// (row_img_byte addresses within each half). Thread t moves the 16 B at
+// column scol = (t&7)*8 of rows srow = t>>3 and srow+32: two 16-B loads, held
+// in registers across the tile's compute, then two 16-B ds_writes.
+// ---------------------------------------------------------------------------
+constexpr int kHalfImg = 4096;       // one 32-row half
+constexpr int kImg = 2 * kHalfImg;   // one 64-row image
+
+// Image `buf` (0/1) of a double-buffered pair that starts at `base`.
+__device__ __forceinline__ char* img(char* base, int buf) {
+  return base + buf * kImg;
+}
+
+struct RowPair {
+  uint4 a, b;  // this thread's 16 B of rows srow and srow+32
+};
+
+// r0, r1: the (clamped) global rows that land in image rows srow, srow+32.
+__device__ __forceinline__ RowPair ld_pair(const __bf16* g, long ss, long r0,
+                                           long r1, int scol) {
+  return {*reinterpret_cast<const uint4*>(g + r0 * ss + scol),
+          *reinterpret_cast<const uint4*>(g + r1 * ss + scol)};
+}
+
+__device__ __forceinline__ void st_pair(char* im, int srow, int scol,
+                                        const RowPair& x) {
+  *reinterpret_cast<uint4*>(im + row_img_byte(srow, scol)) = x.a;
+  *reinterpret_cast<uint4*>(im + kHalfImg + row_img_byte(srow, scol)) = x.b;
+}
+
+// The dkv kernel's side tile: lse*log2e and delta of a q tile's 64 rows, as
+// two double-buffered float[64] pairs (lse2 at [0,128), delta at [128,256)),
+// staged by threads 0..63 alongside the row images.
+constexpr int kSideDelta = 128;
+
+struct SideVal {
+  float lse2, delta;
+};
+
+__device__ __forceinline__ SideVal ld_side(const float* lseg,
+                                           const float* deltag, int row) {
+  return {lseg[row] * kLog2e, deltag[row]};
+}
+
+// Buffer `buf` of the lse2 tile; its delta twin is kSideDelta floats on.
+__device__ __forceinline__ float* side_buf(float* side, int buf) {
+  return side + (buf ? 64 : 0);
+}
+
+// Two stores off two bases with one unsigned index: spelled as one base
+// plus a constant, the dkv kernel takes one more VGPR.
+__device__ __forceinline__ void st_side(float* side, int buf, unsigned i,
+                                        const SideVal& x) {
+  side[(buf ? 64 : 0) + i] = x.lse2;
+  (side + kSideDelta)[(buf ? 64 : 0) + i] = x.delta;
+}
+
+// Four f32 -> four bf16 (round to nearest even), one 8-byte store.
+__device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
+                                            float c, float d) {
+  unsigned lo, hi;
+  asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
+      "v_cvt_pk_bf16_f32 %1, %4, %5"
+      : "=&v"(lo), "=&v"(hi)
+      : "v"(a), "v"(b), "v"(c), "v"(d));
+  uint2 st = {lo, hi};
+  *reinterpret_cast<uint2*>(dst) = st;
+}
+
+// exp2(s*c1 - off): P against the running max (forward, off = m*c1) or the
+// saved logsumexp (backward, off = lse*log2e).
+__device__ __forceinline__ float p_elem(float s, float c1, float off) {
+  return __builtin_amdgcn_exp2f(__builtin_fmaf(s, c1, -off));
+}
+
+// dS = P * (dP - D) * scale
+__device__ __forceinline__ float ds_elem(float pe, float dp, float delta,
+                                         float scale) {
+  return pe * (dp - delta) * scale;
+}
+
+// ---------------------------------------------------------------------------
 // Forward.
 // Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
 // qt*128 + w*32 .. +31.
@@ -192,11 +182,10 @@ __device__ __forceinline__ int ld_row32(int row, int S) {
 template <bool kCausal, bool kRagged>
 __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
-  // 64-row KV tiles, double-buffered: [64][64] bf16 images as two 32-row
-  // halves (row_img_byte addresses within each half).
-  __shared__ __attribute__((aligned(16))) char smem[4 * 8192];
-#define kimg(i) (smem + (i) * 8192)
-#define vimg(i) (smem + 16384 + (i) * 8192)
+  // 64-row KV tiles, double-buffered: K images, then V images.
+  __shared__ __attribute__((aligned(16))) char smem[4 * kImg];
+  char* const kimg = smem;
+  char* const vimg = smem + 2 * kImg;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -205,10 +194,10 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   const int bh = blockIdx.y;
   const int b = bh / p.H, h = bh % p.H;
 
-  const __bf16* qg = p.q + (long)b * p.qs.sb + (long)h * p.qs.sh;
-  const __bf16* kg = p.k + (long)b * p.ks.sb + (long)h * p.ks.sh;
-  const __bf16* vg = p.v + (long)b * p.vs.sb + (long)h * p.vs.sh;
-  __bf16* og = p.o + (long)b * p.os.sb + (long)h * p.os.sh;
+  const __bf16* qg = plane(p.q, p.qs, b, h);
+  const __bf16* kg = plane(p.k, p.ks, b, h);
+  const __bf16* vg = plane(p.v, p.vs, b, h);
+  __bf16* og = plane(p.o, p.os, b, h);
   float* lseg = p.lse + (long)bh * p.S;
 
   const int qb = qt * kQT + wave * 32;      // this wave's first q row
@@ -238,34 +227,26 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   // 64-row tiles: up to the diagonal (causal) or all of them
   const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
 
-  // prologue: stage tile 0 (rows srow and srow+32 of K and V)
+  // prologue: stage tile 0
   {
     const long r0 = ld_row<kRagged>((long)srow, p.S);
     const long r1 = ld_row<kRagged>((long)(srow + 32), p.S);
-    *reinterpret_cast<uint4*>(kimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + r0 * p.ks.ss + scol);
-    *reinterpret_cast<uint4*>(kimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + r1 * p.ks.ss + scol);
-    *reinterpret_cast<uint4*>(vimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + r0 * p.vs.ss + scol);
-    *reinterpret_cast<uint4*>(vimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + r1 * p.vs.ss + scol);
+    st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
+    st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
   }
   __syncthreads();
 
   int cur = 0;
   for (int t = 0; t < n64; ++t) {
     // issue next tile's staging loads early; writes land after compute
-    uint4 nk0, nk1, nv0, nv1;
+    RowPair nk, nv;
     const bool pref = t + 1 < n64;
     if (pref) {
       const long kb = (long)(t + 1) * 64 + srow;
       const long kb0 = ld_row<kRagged>(kb, p.S);
       const long kb1 = ld_row<kRagged>(kb + 32, p.S);
-      nk0 = *reinterpret_cast<const uint4*>(kg + kb0 * p.ks.ss + scol);
-      nk1 = *reinterpret_cast<const uint4*>(kg + kb1 * p.ks.ss + scol);
-      nv0 = *reinterpret_cast<const uint4*>(vg + kb0 * p.vs.ss + scol);
-      nv1 = *reinterpret_cast<const uint4*>(vg + kb1 * p.vs.ss + scol);
+      nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
+      nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
     }
 
 #pragma unroll
@@ -277,8 +258,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
         // wave-uniform: a half-tile or a wave that is all padding
         if (kbase >= p.S || qb >= p.S) break;
       }
-      const char* ki = kimg(cur) + half * 4096;
-      const char* vi = vimg(cur) + half * 4096;
+      const char* ki = img(kimg, cur) + half * kHalfImg;
+      const char* vi = img(vimg, cur) + half * kHalfImg;
 
       // S^T tile: C[k][q] = sum_d K[k][d] * Q[q][d]
       f32x16 s = {};
@@ -324,7 +305,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
       float psum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(pv[r], c1, -mc));
+        pv[r] = p_elem(pv[r], c1, mc);
         psum += pv[r];
       }
       ssum += psum;
@@ -343,14 +324,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
     }
 
     if (pref) {
-      *reinterpret_cast<uint4*>(kimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nk0;
-      *reinterpret_cast<uint4*>(kimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nk1;
-      *reinterpret_cast<uint4*>(vimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nv0;
-      *reinterpret_cast<uint4*>(vimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nv1;
+      st_pair(img(kimg, cur ^ 1), srow, scol, nk);
+      st_pair(img(vimg, cur ^ 1), srow, scol, nv);
     }
     __syncthreads();
     cur ^= 1;
@@ -368,21 +343,12 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   for (int db = 0; db < 2; ++db) {
     const f32x16& a = db ? acc1 : acc0;
 #pragma unroll
-    for (int mq = 0; mq < 4; ++mq) {
-      const int d0 = db * 32 + 8 * mq + 4 * hi;
-      unsigned lo, hi2;
-      asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
-          "v_cvt_pk_bf16_f32 %1, %4, %5"
-          : "=&v"(lo), "=&v"(hi2)
-          : "v"(a[4 * mq] * inv), "v"(a[4 * mq + 1] * inv),
-            "v"(a[4 * mq + 2] * inv), "v"(a[4 * mq + 3] * inv));
-      uint2 st = {lo, hi2};
-      *reinterpret_cast<uint2*>(orow + d0) = st;
-    }
+    for (int mq = 0; mq < 4; ++mq)
+      store4_bf16(orow + db * 32 + 8 * mq + 4 * hi, a[4 * mq] * inv,
+                  a[4 * mq + 1] * inv, a[4 * mq + 2] * inv,
+                  a[4 * mq + 3] * inv);
   }
 }
-#undef kimg
-#undef vimg
 
 // ---------------------------------------------------------------------------
 // Backward dQ. Grid (ceil(S/128), B*H). Per q-tile, loop kv tiles:
@@ -395,23 +361,6 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 // The prologue also forms D[q] = rowsum(dO*O) from the dO fragments it holds
 // anyway plus one read of O, and stores it to p.delta for the dkv kernel.
 // ---------------------------------------------------------------------------
-struct FaBwdParams {
-  const __bf16* q;
-  const __bf16* k;
-  const __bf16* v;
-  const __bf16* o;
-  const __bf16* dout;
-  const float* lse;      // [B,H,S]
-  float* delta;          // [B,H,S] rowsum(dO*O): written by the dq kernel,
-                         // read by the dkv kernel launched after it
-  __bf16* dq;
-  __bf16* dk;
-  __bf16* dv;
-  TStride qs, ks, vs, os, dos_, dqs, dks, dvs;
-  int H, S;
-  float scale;
-};
-
 // Sum of the 8 bf16 products a[e]*b[e] in f32 (each product is exact),
 // added as a balanced tree over adjacent elements:
 // ((p0+p1)+(p2+p3)) + ((p4+p5)+(p6+p7)). The row sum is kept in this fixed
@@ -438,12 +387,12 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
 }
 
 template <bool kCausal, bool kRagged>
-__global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
+__global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
-  // 64-row KV tiles: K and V row images, double-buffered (2 x 8 KB each).
-  __shared__ __attribute__((aligned(16))) char smem[4 * 8192];
-#define kimg(i) (smem + (i) * 8192)
-#define vimg(i) (smem + 16384 + (i) * 8192)
+  // 64-row KV tiles, double-buffered: K images, then V images.
+  __shared__ __attribute__((aligned(16))) char smem[4 * kImg];
+  char* const kimg = smem;
+  char* const vimg = smem + 2 * kImg;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -452,12 +401,12 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
   const int bh = blockIdx.y;
   const int b = bh / p.H, h = bh % p.H;
 
-  const __bf16* qg = p.q + (long)b * p.qs.sb + (long)h * p.qs.sh;
-  const __bf16* kg = p.k + (long)b * p.ks.sb + (long)h * p.ks.sh;
-  const __bf16* vg = p.v + (long)b * p.vs.sb + (long)h * p.vs.sh;
-  const __bf16* dog = p.dout + (long)b * p.dos_.sb + (long)h * p.dos_.sh;
-  const __bf16* og = p.o + (long)b * p.os.sb + (long)h * p.os.sh;
-  __bf16* dqg = p.dq + (long)b * p.dqs.sb + (long)h * p.dqs.sh;
+  const __bf16* qg = plane(p.q, p.qs, b, h);
+  const __bf16* kg = plane(p.k, p.ks, b, h);
+  const __bf16* vg = plane(p.v, p.vs, b, h);
+  const __bf16* dog = plane(p.dout, p.dos_, b, h);
+  const __bf16* og = plane(p.o, p.os, b, h);
+  __bf16* dqg = plane(p.dq, p.dqs, b, h);
 
   const int qb = qt * kQT + wave * 32;
   const int qrow = qb + (lane & 31);
@@ -496,28 +445,20 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
   {
     const long r0 = ld_row32<kRagged>(srow, p.S);
     const long r1 = ld_row32<kRagged>(srow + 32, p.S);
-    *reinterpret_cast<uint4*>(kimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + r0 * p.ks.ss + scol);
-    *reinterpret_cast<uint4*>(kimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(kg + r1 * p.ks.ss + scol);
-    *reinterpret_cast<uint4*>(vimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + r0 * p.vs.ss + scol);
-    *reinterpret_cast<uint4*>(vimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(vg + r1 * p.vs.ss + scol);
+    st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
+    st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
   }
   __syncthreads();
 
   int cur = 0;
   for (int t = 0; t < n64; ++t) {
-    uint4 nk0, nk1, nv0, nv1;
+    RowPair nk, nv;
     const bool pref = t + 1 < n64;
     if (pref) {
       const long kb0 = ld_row32<kRagged>((t + 1) * 64 + srow, p.S);
       const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, p.S);
-      nk0 = *reinterpret_cast<const uint4*>(kg + kb0 * p.ks.ss + scol);
-      nk1 = *reinterpret_cast<const uint4*>(kg + kb1 * p.ks.ss + scol);
-      nv0 = *reinterpret_cast<const uint4*>(vg + kb0 * p.vs.ss + scol);
-      nv1 = *reinterpret_cast<const uint4*>(vg + kb1 * p.vs.ss + scol);
+      nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
+      nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
     }
 
 #pragma unroll
@@ -528,8 +469,8 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
       } else if (kRagged) {
         if (kbase >= p.S || qb >= p.S) break;  // all padding
       }
-      const char* ki = kimg(cur) + half * 4096;
-      const char* vi = vimg(cur) + half * 4096;
+      const char* ki = img(kimg, cur) + half * kHalfImg;
+      const char* vi = img(vimg, cur) + half * kHalfImg;
 
       f32x16 s = {}, dp = {};
       __builtin_amdgcn_s_setprio(1);
@@ -540,24 +481,21 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
       }
       __builtin_amdgcn_s_setprio(0);
 
+      // two loops on purpose: the unmasked one carries no compare
       float ds[16];
       if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
-          const float pe =
-              (kCausal ? kglob > qrow : kglob >= p.S)
-                  ? 0.f
-                  : __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lse2));
-          ds[r] = pe * (dp[r] - dvq) * p.scale;
+          const float pe = (kCausal ? kglob > qrow : kglob >= p.S)
+                               ? 0.f
+                               : p_elem(s[r], c1, lse2);
+          ds[r] = ds_elem(pe, dp[r], dvq, p.scale);
         }
       } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pe =
-              __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lse2));
-          ds[r] = pe * (dp[r] - dvq) * p.scale;
-        }
+        for (int r = 0; r < 16; ++r)
+          ds[r] = ds_elem(p_elem(s[r], c1, lse2), dp[r], dvq, p.scale);
       }
       const bf16x8 d0 = pack_frag(&ds[0]);
       const bf16x8 d1 = pack_frag(&ds[8]);
@@ -570,14 +508,8 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
     }
 
     if (pref) {
-      *reinterpret_cast<uint4*>(kimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nk0;
-      *reinterpret_cast<uint4*>(kimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nk1;
-      *reinterpret_cast<uint4*>(vimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nv0;
-      *reinterpret_cast<uint4*>(vimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nv1;
+      st_pair(img(kimg, cur ^ 1), srow, scol, nk);
+      st_pair(img(vimg, cur ^ 1), srow, scol, nv);
     }
     __syncthreads();
     cur ^= 1;
@@ -589,22 +521,11 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
   for (int db = 0; db < 2; ++db) {
     const f32x16& a = db ? dacc1 : dacc0;
 #pragma unroll
-    for (int mq = 0; mq < 4; ++mq) {
-      const int d0 = db * 32 + 8 * mq + 4 * hi;
-      unsigned lo, hi2;
-      asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
-          "v_cvt_pk_bf16_f32 %1, %4, %5"
-          : "=&v"(lo), "=&v"(hi2)
-          : "v"(a[4 * mq]), "v"(a[4 * mq + 1]), "v"(a[4 * mq + 2]),
-            "v"(a[4 * mq + 3]));
-      uint2 st = {lo, hi2};
-      *reinterpret_cast<uint2*>(drow + d0) = st;
-    }
+    for (int mq = 0; mq < 4; ++mq)
+      store4_bf16(drow + db * 32 + 8 * mq + 4 * hi, a[4 * mq], a[4 * mq + 1],
+                  a[4 * mq + 2], a[4 * mq + 3]);
   }
 }
-#undef kimg
-#undef vimg
-
 
 // ---------------------------------------------------------------------------
 // Backward dK/dV. Grid (ceil(S/128), B*H); wave owns kv rows kt*128+w*32..+31,
@@ -616,16 +537,15 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaBwdParams p) {
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
 template <bool kCausal, bool kRagged>
-__global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
+__global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
-  // 64-row q tiles: Q and dO row images, double-buffered (2 x 8 KB each),
-  // plus lse/delta broadcast tiles; the epilogue reuses [0,32K) as
-  // per-wave f32 scratch for the coalesced dV/dK stores.
-  __shared__ __attribute__((aligned(16))) char smem[4 * 8192 + 1024];
-#define qimg(i) (smem + (i) * 8192)
-#define doimg(i) (smem + 16384 + (i) * 8192)
-#define lsetile (reinterpret_cast<float*>(smem + 32768))
-#define dtile (reinterpret_cast<float*>(smem + 32768 + 512))
+  // 64-row q tiles, double-buffered: Q images, then dO images, then the
+  // lse2/delta side tile; the epilogue reuses [0,32K) as per-wave f32
+  // scratch for the coalesced dV/dK stores.
+  __shared__ __attribute__((aligned(16))) char smem[4 * kImg + 1024];
+  char* const qimg = smem;
+  char* const doimg = smem + 2 * kImg;
+  float* const side = reinterpret_cast<float*>(smem + 4 * kImg);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -634,12 +554,12 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
   const int bh = blockIdx.y;
   const int b = bh / p.H, h = bh % p.H;
 
-  const __bf16* qg = p.q + (long)b * p.qs.sb + (long)h * p.qs.sh;
-  const __bf16* kg = p.k + (long)b * p.ks.sb + (long)h * p.ks.sh;
-  const __bf16* vg = p.v + (long)b * p.vs.sb + (long)h * p.vs.sh;
-  const __bf16* dog = p.dout + (long)b * p.dos_.sb + (long)h * p.dos_.sh;
-  __bf16* dkg = p.dk + (long)b * p.dks.sb + (long)h * p.dks.sh;
-  __bf16* dvg = p.dv + (long)b * p.dvs.sb + (long)h * p.dvs.sh;
+  const __bf16* qg = plane(p.q, p.qs, b, h);
+  const __bf16* kg = plane(p.k, p.ks, b, h);
+  const __bf16* vg = plane(p.v, p.vs, b, h);
+  const __bf16* dog = plane(p.dout, p.dos_, b, h);
+  __bf16* dkg = plane(p.dk, p.dks, b, h);
+  __bf16* dvg = plane(p.dv, p.dvs, b, h);
   const float* lseg = p.lse + (long)bh * p.S;
   const float* deltag = p.delta + (long)bh * p.S;
 
@@ -666,44 +586,34 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
   const int t0 = kCausal ? kt : 0;          // first 64-row q tile
   const int n64 = (p.S + 63) / 64;
 
-  // stage q/dO tile t0 (rows t0*64 + srow, + srow+32)
+  // stage q/dO tile t0 and its side tile
   {
     const int qb0 = t0 * 64;
     const long r0 = ld_row32<kRagged>(qb0 + srow, p.S);
     const long r1 = ld_row32<kRagged>(qb0 + srow + 32, p.S);
-    *reinterpret_cast<uint4*>(qimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(qg + r0 * p.qs.ss + scol);
-    *reinterpret_cast<uint4*>(qimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(qg + r1 * p.qs.ss + scol);
-    *reinterpret_cast<uint4*>(doimg(0) + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(dog + r0 * p.dos_.ss + scol);
-    *reinterpret_cast<uint4*>(doimg(0) + 4096 + row_img_byte(srow, scol)) =
-        *reinterpret_cast<const uint4*>(dog + r1 * p.dos_.ss + scol);
+    st_pair(img(qimg, 0), srow, scol, ld_pair(qg, p.qs.ss, r0, r1, scol));
+    st_pair(img(doimg, 0), srow, scol, ld_pair(dog, p.dos_.ss, r0, r1, scol));
     if (threadIdx.x < 64) {
       const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, p.S);
-      lsetile[threadIdx.x] = lseg[rq] * kLog2e;
-      dtile[threadIdx.x] = deltag[rq];
+      st_side(side, 0, threadIdx.x, ld_side(lseg, deltag, rq));
     }
   }
   __syncthreads();
 
   int cur = 0;
   for (int t = t0; t < n64; ++t) {
-    uint4 nq0, nq1, nd0, nd1;
-    float nlse = 0.f, ndel = 0.f;
+    RowPair nq, nd;
+    SideVal ns = {0.f, 0.f};
     const bool pref = t + 1 < n64;
     if (pref) {
       const int qb1 = (t + 1) * 64;
       const long r0 = ld_row32<kRagged>(qb1 + srow, p.S);
       const long r1 = ld_row32<kRagged>(qb1 + srow + 32, p.S);
-      nq0 = *reinterpret_cast<const uint4*>(qg + r0 * p.qs.ss + scol);
-      nq1 = *reinterpret_cast<const uint4*>(qg + r1 * p.qs.ss + scol);
-      nd0 = *reinterpret_cast<const uint4*>(dog + r0 * p.dos_.ss + scol);
-      nd1 = *reinterpret_cast<const uint4*>(dog + r1 * p.dos_.ss + scol);
+      nq = ld_pair(qg, p.qs.ss, r0, r1, scol);
+      nd = ld_pair(dog, p.dos_.ss, r0, r1, scol);
       if (threadIdx.x < 64) {
         const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, p.S);
-        nlse = lseg[rq] * kLog2e;
-        ndel = deltag[rq];
+        ns = ld_side(lseg, deltag, rq);
       }
     }
 
@@ -716,10 +626,10 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
         // wave-uniform: a q half-tile or a k-row wave that is all padding
         if (qbase >= p.S || kbb >= p.S) break;
       }
-      const char* qi = qimg(cur) + half * 4096;
-      const char* di = doimg(cur) + half * 4096;
-      const float* lsec = lsetile + (cur ? 64 : 0) + half * 32;
-      const float* dc = dtile + (cur ? 64 : 0) + half * 32;
+      const char* qi = img(qimg, cur) + half * kHalfImg;
+      const char* di = img(doimg, cur) + half * kHalfImg;
+      const float* lsec = side_buf(side, cur) + half * 32;
+      const float* dc = lsec + kSideDelta;
 
       f32x16 sacc = {}, dp = {};
       __builtin_amdgcn_s_setprio(1);
@@ -730,27 +640,23 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
       }
       __builtin_amdgcn_s_setprio(0);
 
+      // two loops on purpose: the unmasked one carries no compare
       float pv[16], ds[16];
       if (kCausal ? qbase < kbb + 31 : kRagged && qbase + 31 >= p.S) {
         // diagonal: mask q < k; ragged: mask the q rows past S-1
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qglob = qbase + crow(r, hi);
-          const float pe =
-              (kCausal ? qglob < krow : qglob >= p.S)
-                  ? 0.f
-                  : __builtin_amdgcn_exp2f(
-                        __builtin_fmaf(sacc[r], c1, -lsec[crow(r, hi)]));
-          pv[r] = pe;
-          ds[r] = pe * (dp[r] - dc[crow(r, hi)]) * p.scale;
+          pv[r] = (kCausal ? qglob < krow : qglob >= p.S)
+                      ? 0.f
+                      : p_elem(sacc[r], c1, lsec[crow(r, hi)]);
+          ds[r] = ds_elem(pv[r], dp[r], dc[crow(r, hi)], p.scale);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float pe = __builtin_amdgcn_exp2f(
-              __builtin_fmaf(sacc[r], c1, -lsec[crow(r, hi)]));
-          pv[r] = pe;
-          ds[r] = pe * (dp[r] - dc[crow(r, hi)]) * p.scale;
+          pv[r] = p_elem(sacc[r], c1, lsec[crow(r, hi)]);
+          ds[r] = ds_elem(pv[r], dp[r], dc[crow(r, hi)], p.scale);
         }
       }
       const bf16x8 p0 = pack_frag(&pv[0]);
@@ -772,18 +678,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
     }
 
     if (pref) {
-      *reinterpret_cast<uint4*>(qimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nq0;
-      *reinterpret_cast<uint4*>(qimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nq1;
-      *reinterpret_cast<uint4*>(doimg(cur ^ 1) + row_img_byte(srow, scol)) =
-          nd0;
-      *reinterpret_cast<uint4*>(doimg(cur ^ 1) + 4096 +
-                                row_img_byte(srow, scol)) = nd1;
-      if (threadIdx.x < 64) {
-        lsetile[((cur ^ 1) ? 64 : 0) + threadIdx.x] = nlse;
-        dtile[((cur ^ 1) ? 64 : 0) + threadIdx.x] = ndel;
-      }
+      st_pair(img(qimg, cur ^ 1), srow, scol, nq);
+      st_pair(img(doimg, cur ^ 1), srow, scol, nd);
+      if (threadIdx.x < 64) st_side(side, cur ^ 1, threadIdx.x, ns);
     }
     __syncthreads();
     cur ^= 1;
@@ -810,83 +707,58 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaBwdParams p) {
 #pragma unroll
     for (int mq = 0; mq < 8; ++mq) {
       const float* src = scratch + row * 64 + dhalf + mq * 4;
-      unsigned lo, hi2;
-      asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
-          "v_cvt_pk_bf16_f32 %1, %4, %5"
-          : "=&v"(lo), "=&v"(hi2)
-          : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]));
-      uint2 st = {lo, hi2};
       if (!kRagged || kbb + row < p.S)
-        *reinterpret_cast<uint2*>(outg + (long)(kbb + row) * os.ss + dhalf +
-                                  mq * 4) = st;
+        store4_bf16(outg + (long)(kbb + row) * os.ss + dhalf + mq * 4, src[0],
+                    src[1], src[2], src[3]);
     }
     __syncthreads();  // scratch reused for dK after dV drains
   }
 }
-#undef qimg
-#undef doimg
-#undef lsetile
-#undef dtile
 
 // ---------------------------------------------------------------------------
-// MFMA layout probe: C = A·B for one 32x32x16 tile with the documented
-// fragment mappings; lets a GPU test verify the lane->element maps
-// independently of the attention kernels.
+// Host side.
 // ---------------------------------------------------------------------------
-// tr-read probe: fill a swizzled row image with X[k][d] = k*64+d (bf16),
-// run read_tr_frag for (kb, db) and dump each lane's 8 fragment elements
-// -> out[lane][e]; a test checks lane l elem e == X[kb*16+8*(l>>5)+e][db*32+(l&31)].
-__global__ void tr_probe_kernel(float* out, int kb, int db) {
-  __shared__ __attribute__((aligned(16))) char img[4096];
-  const int lane = threadIdx.x & 63;
-  for (int i = threadIdx.x; i < 2048; i += 64) {
-    const int k = i / 64, d = i % 64;
-    *reinterpret_cast<__bf16*>(img + row_img_byte(k, d)) =
-        (__bf16)(float)(k * 64 + d);
-  }
-  __syncthreads();
-  bf16x8 f = read_tr_frag(img, lane, kb, db);
-  union {
-    bf16x8 v;
-    __bf16 e[8];
-  } u;
-  u.v = f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) out[lane * 8 + e] = (float)u.e[e];
+TStride stride_at(const long* s, int i) {
+  return {s[3 * i], s[3 * i + 1], s[3 * i + 2]};
 }
 
-// pack probe: lane provides p[r] = lane*100 + r; dump the packed fragment.
-__global__ void pack_probe_kernel(float* out) {
-  const int lane = threadIdx.x & 63;
-  float p[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) p[r] = (float)(lane * 100 + r);
-  bf16x8 f = pack_frag(p);
-  union {
-    bf16x8 v;
-    __bf16 e[8];
-  } u;
-  u.v = f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) out[lane * 8 + e] = (float)u.e[e];
+void check_len(const char* name, int S, bool causal) {
+  if (S < 1) throw std::runtime_error(std::string(name) + ": S < 1");
+  if (causal && S % kQT != 0)
+    throw std::runtime_error(std::string(name) +
+                             ": causal needs S % 128 == 0");
 }
 
-__global__ void mfma_probe_kernel(const __bf16* a, const __bf16* b, float* c) {
-  const int lane = threadIdx.x & 63;
-  union {
-    __bf16 e[8];
-    bf16x8 f;
-  } af, bf;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    af.e[e] = a[(lane % 32) * 16 + 8 * (lane / 32) + e];   // A[i][k]
-    bf.e[e] = b[(8 * (lane / 32) + e) * 32 + (lane % 32)]; // B[k][j]
-  }
-  f32x16 acc = {};
-  acc = mfma(af.f, bf.f, acc);
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    c[crow(r, lane >> 5) * 32 + (lane % 32)] = acc[r];
+// Calls f(kCausal, kRagged) with the mode as two std::bool_constant values.
+template <typename F>
+void with_mode(bool causal, int S, F&& f) {
+  if (causal)
+    f(std::true_type{}, std::false_type{});
+  else if (S % kQT == 0)
+    f(std::false_type{}, std::false_type{});
+  else
+    f(std::false_type{}, std::true_type{});
+}
+
+// The part of the parameter block that both directions fill. strides: 3 per
+// tensor, q, k, v, o first.
+FaParams fwd_params(const void* q, const void* k, const void* v, void* o,
+                    float* lse, int H, int S, const long* strides,
+                    float scale) {
+  FaParams p = {};
+  p.q = (const __bf16*)q;
+  p.k = (const __bf16*)k;
+  p.v = (const __bf16*)v;
+  p.o = (__bf16*)o;
+  p.lse = lse;
+  p.qs = stride_at(strides, 0);
+  p.ks = stride_at(strides, 1);
+  p.vs = stride_at(strides, 2);
+  p.os = stride_at(strides, 3);
+  p.H = H;
+  p.S = S;
+  p.scale = scale;
+  return p;
 }
 
 }  // namespace
@@ -897,96 +769,41 @@ __global__ void mfma_probe_kernel(const __bf16* a, const __bf16* b, float* c) {
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal) {
-  if (S < 1) throw std::runtime_error("fa_forward: S < 1");
-  if (causal && S % kQT != 0)
-    throw std::runtime_error("fa_forward: causal needs S % 128 == 0");
-  FaParams p;
-  p.q = (const __bf16*)q;
-  p.k = (const __bf16*)k;
-  p.v = (const __bf16*)v;
-  p.o = (__bf16*)o;
-  p.lse = lse;
-  p.qs = {strides[0], strides[1], strides[2]};
-  p.ks = {strides[3], strides[4], strides[5]};
-  p.vs = {strides[6], strides[7], strides[8]};
-  p.os = {strides[9], strides[10], strides[11]};
-  p.H = H;
-  p.S = S;
-  p.scale = scale;
-  dim3 grid((S + kQT - 1) / kQT, B * H);
-  if (causal)
-    hipLaunchKernelGGL((fa_fwd_kernel<true, false>), grid, dim3(256), 0,
-                       stream, p);
-  else if (S % kQT == 0)
-    hipLaunchKernelGGL((fa_fwd_kernel<false, false>), grid, dim3(256), 0,
-                       stream, p);
-  else
-    hipLaunchKernelGGL((fa_fwd_kernel<false, true>), grid, dim3(256), 0,
-                       stream, p);
+  check_len("fa_forward", S, causal);
+  const FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
+  const dim3 grid((S + kQT - 1) / kQT, B * H);
+  with_mode(causal, S, [&](auto c, auto r) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value;
+    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR>), grid, dim3(256), 0, stream, p);
+  });
 }
 
-// strides: q, k, v, o, dO, dq, dk, dv (3 each). delta is a [B,H,S] f32
-// workspace the dq kernel fills and the dkv kernel consumes.
+// strides: q, k, v, o, dO, dq, dk, dv. delta is a [B,H,S] f32 workspace the
+// dq kernel fills and the dkv kernel consumes; o and lse are only read.
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal) {
-  if (S < 1) throw std::runtime_error("fa_backward: S < 1");
-  if (causal && S % kQT != 0)
-    throw std::runtime_error("fa_backward: causal needs S % 128 == 0");
-  FaBwdParams p;
-  p.q = (const __bf16*)q;
-  p.k = (const __bf16*)k;
-  p.v = (const __bf16*)v;
-  p.o = (const __bf16*)o;
+  check_len("fa_backward", S, causal);
+  FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
+                          const_cast<float*>(lse), H, S, strides, scale);
   p.dout = (const __bf16*)do_;
-  p.lse = lse;
   p.delta = delta;
   p.dq = (__bf16*)dq;
   p.dk = (__bf16*)dk;
   p.dv = (__bf16*)dv;
-  p.qs = {strides[0], strides[1], strides[2]};
-  p.ks = {strides[3], strides[4], strides[5]};
-  p.vs = {strides[6], strides[7], strides[8]};
-  p.os = {strides[9], strides[10], strides[11]};
-  p.dos_ = {strides[12], strides[13], strides[14]};
-  p.dqs = {strides[15], strides[16], strides[17]};
-  p.dks = {strides[18], strides[19], strides[20]};
-  p.dvs = {strides[21], strides[22], strides[23]};
-  p.H = H;
-  p.S = S;
-  p.scale = scale;
-  dim3 grid((S + kQT - 1) / kQT, B * H);
-  if (causal) {
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, false>), grid, dim3(256), 0,
-                       stream, p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<true, false>), grid, dim3(256), 0,
-                       stream, p);
-  } else if (S % kQT == 0) {
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false>), grid, dim3(256), 0,
-                       stream, p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<false, false>), grid, dim3(256), 0,
-                       stream, p);
-  } else {
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, true>), grid, dim3(256), 0,
-                       stream, p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<false, true>), grid, dim3(256), 0,
-                       stream, p);
-  }
-}
-
-void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream) {
-  hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, stream,
-                     (const __bf16*)a, (const __bf16*)b, c);
-}
-
-void tr_probe(float* out, int kb, int db, hipStream_t stream) {
-  hipLaunchKernelGGL(tr_probe_kernel, dim3(1), dim3(64), 0, stream, out, kb,
-                     db);
-}
-
-void pack_probe(float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(pack_probe_kernel, dim3(1), dim3(64), 0, stream, out);
+  p.dos_ = stride_at(strides, 4);
+  p.dqs = stride_at(strides, 5);
+  p.dks = stride_at(strides, 6);
+  p.dvs = stride_at(strides, 7);
+  const dim3 grid((S + kQT - 1) / kQT, B * H);
+  with_mode(causal, S, [&](auto c, auto r) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value;
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR>), grid, dim3(256), 0, stream,
+                       p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR>), grid, dim3(256), 0, stream,
+                       p);
+  });
 }
 
 }  // namespace adapcc

@@ -6,18 +6,9 @@ import math
 import pytest
 import torch
 
+from attn_util import ref_attention_f32
+
 pytestmark = pytest.mark.gpu
-
-
-def ref_attention_f32(q, k, v, scale):
-    """fp32 causal attention reference (explicit, no SDPA)."""
-    qf, kf, vf = q.float(), k.float(), v.float()
-    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-    S = q.shape[-2]
-    mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
-    s = s.masked_fill(mask, float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    return torch.matmul(p, vf)
 
 
 def test_mfma_layout_probe():
@@ -96,8 +87,8 @@ def test_fa_fwd_bwd_matches_reference(B, H, S):
     assert fa_supported(q, k, v, True, 0.0)
     scale = 1.0 / math.sqrt(D)
 
-    o = _FlashAttnFn.apply(q, k, v, scale)
-    ref = ref_attention_f32(q, k, v, scale)
+    o = _FlashAttnFn.apply(q, k, v, scale, True)
+    ref = ref_attention_f32(q, k, v, scale, True)
     torch.testing.assert_close(o.float(), ref, rtol=2e-2, atol=2e-2)
 
     g = torch.randn_like(o)
@@ -105,7 +96,7 @@ def test_fa_fwd_bwd_matches_reference(B, H, S):
     qr = q.detach().float().requires_grad_(True)
     kr = k.detach().float().requires_grad_(True)
     vr = v.detach().float().requires_grad_(True)
-    rr = ref_attention_f32(qr, kr, vr, scale)
+    rr = ref_attention_f32(qr, kr, vr, scale, True)
     rr.backward(g.float())
     torch.testing.assert_close(q.grad.float(), qr.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(k.grad.float(), kr.grad, rtol=5e-2, atol=5e-2)
@@ -143,9 +134,9 @@ def test_fa_extreme_values_stable():
     v = torch.randn(B, H, S, D, device="cuda").to(torch.bfloat16)
     scale = 1.0 / math.sqrt(D)
     o = _FlashAttnFn.apply(q.requires_grad_(True), k.requires_grad_(True),
-                           v.requires_grad_(True), scale)
+                           v.requires_grad_(True), scale, True)
     assert torch.isfinite(o.float()).all()
-    ref = ref_attention_f32(q, k, v, scale)
+    ref = ref_attention_f32(q, k, v, scale, True)
     torch.testing.assert_close(o.float(), ref, rtol=3e-2, atol=3e-2)
 
 

@@ -10,6 +10,8 @@ import pytest
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
+from attn_util import ref_attention_f32
+
 pytestmark = pytest.mark.gpu
 
 B, H, D = 2, 3, 64
@@ -19,15 +21,6 @@ SCALE = 1.0 / math.sqrt(D)
 # 128: aligned; 129: second workgroup has one row, dkv sums over two
 # q-tiles; 197: ViT
 SEQS = [1, 33, 64, 65, 128, 129, 197]
-
-
-def ref_attention_f32(q, k, v, scale):
-    """fp32 bidirectional attention reference (explicit, no SDPA): the one
-    of test_gpu_attention.py without the mask."""
-    qf, kf, vf = q.float(), k.float(), v.float()
-    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-    p = torch.softmax(s, dim=-1)
-    return torch.matmul(p, vf)
 
 
 def rand(S, seed, b=B, h=H):
@@ -45,7 +38,7 @@ def test_fwd_bwd_matches_reference(S):
     assert fa_supported(q, k, v, False, 0.0)
 
     o = flash_attention(q, k, v, causal=False)
-    ref = ref_attention_f32(q, k, v, SCALE)
+    ref = ref_attention_f32(q, k, v, SCALE, False)
     torch.testing.assert_close(o.float(), ref, rtol=2e-2, atol=2e-2)
 
     g = rand(S, 3)
@@ -53,7 +46,7 @@ def test_fwd_bwd_matches_reference(S):
     qr = q.detach().float().requires_grad_(True)
     kr = k.detach().float().requires_grad_(True)
     vr = v.detach().float().requires_grad_(True)
-    ref_attention_f32(qr, kr, vr, SCALE).backward(g.float())
+    ref_attention_f32(qr, kr, vr, SCALE, False).backward(g.float())
     torch.testing.assert_close(q.grad.float(), qr.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(k.grad.float(), kr.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(v.grad.float(), vr.grad, rtol=5e-2, atol=5e-2)
@@ -165,7 +158,7 @@ def test_padding_never_written(S):
         assert torch.isfinite(f[:n]).all()
         assert (f[n:] == sent).all()
     # and the rows that are written are right
-    ref = ref_attention_f32(q, k, v, SCALE)
+    ref = ref_attention_f32(q, k, v, SCALE, False)
     torch.testing.assert_close(outs[0][1].float(), ref, rtol=2e-2, atol=2e-2)
 
 
@@ -225,7 +218,7 @@ def test_extreme_values_stable():
     v = torch.randn(1, 2, S, D, device="cuda").to(torch.bfloat16)
     o = flash_attention(q, k, v, causal=False)
     assert torch.isfinite(o.float()).all()
-    ref = ref_attention_f32(q, k, v, SCALE)
+    ref = ref_attention_f32(q, k, v, SCALE, False)
     torch.testing.assert_close(o.float(), ref, rtol=3e-2, atol=3e-2)
 
 

@@ -9,32 +9,12 @@ import math
 import pytest
 import torch
 
+from attn_util import heads, ref_attention_f32, unheads
+
 pytestmark = pytest.mark.gpu
 
 D = 64
 SHAPES = [(1, 1, 128), (2, 3, 256)]
-
-
-def ref_attention_f32(q, k, v, scale):
-    """fp32 causal attention reference (explicit, no SDPA); same as in
-    test_gpu_attention.py."""
-    qf, kf, vf = q.float(), k.float(), v.float()
-    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-    S = q.shape[-2]
-    mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
-    s = s.masked_fill(mask, float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    return torch.matmul(p, vf)
-
-
-def heads(t, H):
-    B, T, C = t.shape
-    return t.view(B, T, H, C // H).transpose(1, 2)
-
-
-def unheads(t):
-    B, H, T, d = t.shape
-    return t.transpose(1, 2).reshape(B, T, H * d)
 
 
 def make_qkv(B, H, S, seed=0):
@@ -47,7 +27,7 @@ def ref_packed_f32(qkv, H, g):
     C = H * D
     x = qkv.detach().float().requires_grad_(True)
     q, k, v = (heads(t, H) for t in x.split(C, dim=2))
-    y = unheads(ref_attention_f32(q, k, v, 1.0 / math.sqrt(D)))
+    y = unheads(ref_attention_f32(q, k, v, 1.0 / math.sqrt(D), True))
     y.backward(g.float())
     return y.detach(), x.grad
 
@@ -72,7 +52,7 @@ def test_packed_equals_unpacked_bitwise(B, H, S):
     # unpacked: _FlashAttnFn on the split views
     q, k, v = (heads(t, H).requires_grad_(True)
                for t in qkv.detach().split(C, dim=2))
-    o = _FlashAttnFn.apply(q, k, v, 1.0 / math.sqrt(D))
+    o = _FlashAttnFn.apply(q, k, v, 1.0 / math.sqrt(D), True)
     o.backward(heads(g, H))
     want_y = unheads(o.detach())
     want_grad = torch.cat([unheads(t.grad) for t in (q, k, v)], dim=2)
