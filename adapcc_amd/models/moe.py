@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.fused import FusedLayerNorm
+from ..ops.moe import moe_combine, moe_dispatch, moe_fusable, moe_route_top1
 
 
 class _AllToAll(torch.autograd.Function):
@@ -67,8 +68,10 @@ class MoEMLP(nn.Module):
         world_size: int = 1,
         rank: int = 0,
         capacity_factor: float = 1.25,
+        fused_routing: bool = True,
     ):
         super().__init__()
+        self.fused_routing = fused_routing
         self.comm = comm
         self.world_size = world_size
         self.rank = rank
@@ -89,6 +92,8 @@ class MoEMLP(nn.Module):
         cap = max(1, math.ceil(T / E * self.capacity_factor))
 
         logits = self.gate(x)
+        if self.fused_routing and moe_fusable(x, logits, cap):
+            return self._forward_fused(x, logits, cap).view(orig_shape)
         probs = logits.softmax(dim=-1)
         gate_p, expert_idx = probs.max(dim=-1)  # top-1
 
@@ -129,6 +134,28 @@ class MoEMLP(nn.Module):
         y = x.new_zeros(T, self.d_model)
         y[keep] = back.index_select(0, kept_slot) * gate_p[keep, None]
         return y.view(orig_shape)
+
+    def _forward_fused(self, x: torch.Tensor, logits: torch.Tensor,
+                       cap: int) -> torch.Tensor:
+        """Same layer on the ops/moe.py kernels: no host sync, no one-hot,
+        no zero-filled buffers. The exchange and the expert loop are those
+        of ``forward``."""
+        routing = moe_route_top1(logits, cap)
+        dispatch = moe_dispatch(x, routing)
+        dispatch = dispatch.view(self.world_size, self.num_local * cap,
+                                 self.d_model)
+        recv = _AllToAll.apply(self.comm, dispatch)
+        recv = recv.view(self.world_size, self.num_local, cap, self.d_model)
+        outs = []
+        for i, expert in enumerate(self.experts):
+            outs.append(expert(recv[:, i].reshape(-1, self.d_model)))
+        out = torch.stack(outs, dim=1)
+        out = out.view(self.world_size, cap, self.num_local, self.d_model)
+        out = out.permute(0, 2, 1, 3).contiguous()
+        back = _AllToAll.apply(
+            self.comm, out.view(self.world_size, self.num_local * cap,
+                                self.d_model))
+        return moe_combine(back.reshape(-1, self.d_model), routing)
 
 
 class MoETransformerBlock(nn.Module):

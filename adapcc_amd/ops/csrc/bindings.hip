@@ -98,6 +98,18 @@ void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
 void gelu_backward(int dtype, const void* x, const void* dy, void* dx, long n,
                    hipStream_t stream);
+void moe_route(int dtype, const void* logits, float* gate_p, int* expert,
+               int* slot, int* src, int* counts, int* offs, int* totals,
+               long ntok, long E, long cap, hipStream_t stream);
+void moe_route_bwd(int dtype, const void* logits, const float* gate_p,
+                   const int* expert, const int* slot, const float* dgate,
+                   void* dlogits, long ntok, long E, hipStream_t stream);
+void moe_gather(int dtype, const void* in, long in_rows, const int* map,
+                const float* scale, int scale_by_src, void* out, long rows,
+                long d, hipStream_t stream);
+void moe_rowdot(int dtype, const void* a, const void* b, long b_rows,
+                const int* map, float* out, long rows, long d,
+                hipStream_t stream);
 void tr_probe(float* out, int kb, int db, hipStream_t stream);
 void pack_probe(float* out, hipStream_t stream);
 }
@@ -240,6 +252,53 @@ PYBIND11_MODULE(_core, m) {
           adapcc::gelu_backward(dtype, (const void*)x, (const void*)dy,
                                 (void*)dx, n,
                                 reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+
+  // Top-1 MoE routing and row movement (moe.hip). counts/offs are int32
+  // workspaces of ceil(T/256)*E elements, totals of E.
+  m.def("moe_route",
+        [](int dtype, uintptr_t logits, uintptr_t gate_p, uintptr_t expert,
+           uintptr_t slot, uintptr_t src, uintptr_t counts, uintptr_t offs,
+           uintptr_t totals, long ntok, long E, long cap, uintptr_t stream) {
+          adapcc::moe_route(dtype, (const void*)logits, (float*)gate_p,
+                            (int*)expert, (int*)slot, (int*)src, (int*)counts,
+                            (int*)offs, (int*)totals, ntok, E, cap,
+                            reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  m.def("moe_route_bwd",
+        [](int dtype, uintptr_t logits, uintptr_t gate_p, uintptr_t expert,
+           uintptr_t slot, uintptr_t dgate, uintptr_t dlogits, long ntok,
+           long E, uintptr_t stream) {
+          adapcc::moe_route_bwd(dtype, (const void*)logits,
+                                (const float*)gate_p, (const int*)expert,
+                                (const int*)slot, (const float*)dgate,
+                                (void*)dlogits, ntok, E,
+                                reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // scale = 0: plain copy; scale_by_src picks scale[map[r]] over scale[r]
+  m.def("moe_gather",
+        [](int dtype, uintptr_t in, long in_rows, uintptr_t map,
+           uintptr_t scale, bool scale_by_src, uintptr_t out, long rows,
+           long d, uintptr_t stream) {
+          adapcc::moe_gather(dtype, (const void*)in, in_rows, (const int*)map,
+                             (const float*)scale, scale_by_src ? 1 : 0,
+                             (void*)out, rows, d,
+                             reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  m.def("moe_rowdot",
+        [](int dtype, uintptr_t a, uintptr_t b, long b_rows, uintptr_t map,
+           uintptr_t out, long rows, long d, uintptr_t stream) {
+          adapcc::moe_rowdot(dtype, (const void*)a, (const void*)b, b_rows,
+                             (const int*)map, (float*)out, rows, d,
+                             reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
