@@ -21,6 +21,7 @@ class ViTConfig:
     depth: int = 12
     heads: int = 12
     mlp_dim: int = 3072
+    attn_dropout: float = 0.0   # on the attention probabilities, training
 
     @classmethod
     def base(cls) -> "ViTConfig":
@@ -33,8 +34,10 @@ class ViTConfig:
 
 
 class EncoderBlock(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_dim: int):
+    def __init__(self, dim: int, heads: int, mlp_dim: int,
+                 attn_dropout: float = 0.0):
         super().__init__()
+        self.attn_dropout = attn_dropout
         self.ln1 = FusedLayerNorm(dim)
         self.qkv = nn.Linear(dim, 3 * dim)
         self.proj = nn.Linear(dim, dim)
@@ -49,8 +52,10 @@ class EncoderBlock(nn.Module):
         # bf16 with head_dim 64 on the GPU runs the non-causal flash
         # attention kernels on the packed projection; anything else composes
         # to SDPA on its head views
-        a = attention.flash_attention_qkv(self.qkv(h), self.heads,
-                                          causal=False)
+        a = attention.flash_attention_qkv(
+            self.qkv(h), self.heads,
+            dropout_p=self.attn_dropout if self.training else 0.0,
+            causal=False)
         x = x + self.proj(a)
         x = x + self.mlp(self.ln2(x))
         return x
@@ -66,7 +71,7 @@ class ViT(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, cfg.dim))
         self.pos = nn.Parameter(torch.zeros(1, n_patches + 1, cfg.dim))
         self.blocks = nn.ModuleList(
-            EncoderBlock(cfg.dim, cfg.heads, cfg.mlp_dim)
+            EncoderBlock(cfg.dim, cfg.heads, cfg.mlp_dim, cfg.attn_dropout)
             for _ in range(cfg.depth)
         )
         self.ln = FusedLayerNorm(cfg.dim)

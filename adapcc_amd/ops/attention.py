@@ -1,25 +1,38 @@
 """Hand-written CDNA4 flash attention (csrc/attn.hip) with autograd.
 
 Supported fast paths, both bf16, head_dim 64, self-attention (q, k, v of one
-shape), no dropout: causal with seq len a multiple of 128 (GPT-2), and
-non-causal with any seq len >= 1 (ViT: 197). Anything else falls back to
-torch SDPA. Tensors are [B, H, S, D] with any batch/head/row strides (rows
-must be contiguous and 16-B aligned), so the usual
+shape), attention dropout 0 <= p < 1: causal with seq len a multiple of 128
+(GPT-2), and non-causal with any seq len >= 1 (ViT: 197). Anything else
+falls back to torch SDPA. Tensors are [B, H, S, D] with any batch/head/row
+strides (rows must be contiguous and 16-B aligned), so the usual
 ``.view(B,T,H,hd).transpose(1,2)`` projection views work without a copy.
 ``flash_attention_qkv`` takes the packed [B,T,3C] projection and returns
 [B,T,C], reading and writing both layouts in place, in either mode.
+
+Dropout acts on the attention probabilities inside the kernels. The mask is
+a pure function keep(seed, b*H+h, q, k) (csrc/attn_drop.h) that the backward
+regenerates, never a stored tensor; kept probabilities are multiplied by
+1/(1-p). The 64-bit seed is one int64 on the device, read when the kernels
+run: drawn from torch's generator per call (so ``torch.manual_seed``
+reproduces a run, without a host sync, and a captured graph that refills it
+sees a fresh mask on every replay), or passed as ``dropout_seed``. It is
+this project's own stream, not the Philox one of torch SDPA.
+``dropout_keep_mask_reference`` is the same function in torch integer ops,
+``fa_dropout_mask`` the kernels' own answer.
 """
 
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 
 from .fused import _core
 
 __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
-           "fa_qkv_supported"]
+           "fa_qkv_supported", "fa_dropout_mask",
+           "dropout_keep_mask_reference"]
 
 
 def _strides3(t: torch.Tensor):
@@ -38,8 +51,11 @@ def _row_ok(t: torch.Tensor) -> bool:
 def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
                dropout_p: float) -> bool:
     """What the kernels take, layout aside: bf16 on the GPU, head_dim 64,
-    S >= 1 (a multiple of 128 when causal), no dropout, extension built."""
-    if dropout_p != 0.0 or not (t.is_cuda and t.dtype == torch.bfloat16):
+    S >= 1 (a multiple of 128 when causal), 0 <= dropout_p < 1, extension
+    built."""
+    if not 0.0 <= dropout_p < 1.0:
+        return False
+    if not (t.is_cuda and t.dtype == torch.bfloat16):
         return False
     if D != 64 or S < 1 or (causal and S % 128 != 0):
         return False
@@ -55,19 +71,97 @@ def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return _kernel_ok(q, q.shape[3], q.shape[2], causal, dropout_p)
 
 
-def _launch_fwd(q, k, v, o, lse, scale, causal=True):
+# ---------------------------------------------------------------------------
+# Dropout mask
+# ---------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+
+
+def _drop_threshold(p: float) -> int:
+    """keep iff word >= thr; round() ties to even, as the launcher does."""
+    return min(max(round(p * 2 ** 32), 1), 2 ** 32 - 1)
+
+
+def _fmix(x: torch.Tensor) -> torch.Tensor:
+    # 32-bit values carried in int64: a product wraps mod 2^64, which keeps
+    # its low 32 bits right; every shift sees a masked, non-negative value
+    x = x ^ (x >> 16)
+    x = (x * 0x85EBCA6B) & _M32
+    x = x ^ (x >> 13)
+    x = (x * 0xC2B2AE35) & _M32
+    return x ^ (x >> 16)
+
+
+def dropout_keep_mask_reference(seed, B: int, H: int, S: int,
+                                p: float) -> torch.Tensor:
+    """The kernels' keep(seed, bh, q, k) as a [B,H,S,S] bool tensor on the
+    CPU, in torch integer ops (csrc/attn_drop.h is the definition). seed:
+    int or one-element int64 tensor."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed_lo, seed_hi = seed & _M32, seed >> 32
+    bh = torch.arange(B * H, dtype=torch.int64).view(-1, 1)
+    r = torch.arange(S, dtype=torch.int64).view(1, -1)
+    a = _fmix((seed_lo + bh * 0x9E3779B1 + r * 0x85EBCA77) & _M32)
+    b = _fmix(((seed_hi ^ ((bh * 0xC2B2AE3D) & _M32))
+               + r * 0x27D4EB2F) & _M32)
+    x = (a.view(B * H, S, 1) + b.view(B * H, 1, S)) & _M32
+    x = (x * 0x2C1B3C6D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x297A2D39) & _M32
+    x = x ^ (x >> 15)
+    return (x >= _drop_threshold(p)).view(B, H, S, S)
+
+
+def fa_dropout_mask(seed, B: int, H: int, S: int, p: float) -> torch.Tensor:
+    """[B,H,S,S] bool, True where attention dropout at rate p keeps the
+    probability. seed: one-element int64 tensor (or an int). A seed tensor
+    on the GPU is answered by the kernels' own device function, anything
+    else by the replica."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError("fa_dropout_mask: need 0 <= p < 1")
+    if isinstance(seed, torch.Tensor) and seed.is_cuda:
+        core = _core()
+        if not core:
+            raise RuntimeError("fa_dropout_mask: native extension missing")
+        s = _seed_tensor(seed, seed.device)
+        out = torch.empty((B, H, S, S), dtype=torch.uint8, device=s.device)
+        stream = torch.cuda.current_stream(s.device).cuda_stream
+        core.fa_dropout_mask(out.data_ptr(), s.data_ptr(), B, H, S, p,
+                             stream)
+        return out.bool()
+    return dropout_keep_mask_reference(seed, B, H, S, p)
+
+
+def _seed_tensor(seed: Optional[torch.Tensor],
+                 device: torch.device) -> torch.Tensor:
+    """The one-element int64 device tensor the kernels read the seed from;
+    drawn from torch's generator on the device when none is given."""
+    if seed is None:
+        return torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64,
+                             device=device)
+    if (seed.dtype != torch.int64 or seed.numel() != 1
+            or seed.device != device):
+        raise ValueError("dropout_seed: need a one-element int64 tensor on "
+                         "the inputs' device")
+    return seed.view(1)
+
+
+def _launch_fwd(q, k, v, o, lse, scale, causal=True, dropout_p=0.0,
+                seed=None):
     B, H, S, _ = q.shape
     strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                   lse.data_ptr(), B, H, S, strides, scale, stream, causal)
+                   lse.data_ptr(), B, H, S, strides, scale, stream, causal,
+                   dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0)
 
 
 def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
-                delta=None):
+                delta=None, dropout_p=0.0, seed=None):
     """dq/dk/dv are written in place; delta = rowsum(dO*O) is computed by
     the dq kernel into a workspace (``delta``: contiguous [B,H,S] fp32, made
-    here when not given) the dkv kernel then reads."""
+    here when not given) the dkv kernel then reads. With dropout, ``seed``
+    is the forward's seed tensor."""
     B, H, S, _ = q.shape
     # e.g. y.sum().backward() hands down an expanded, zero-stride dout
     do = dout if _row_ok(dout) else dout.contiguous()
@@ -80,19 +174,21 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
     _core().fa_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
-                   strides, scale, stream, causal)
+                   strides, scale, stream, causal, dropout_p,
+                   seed.data_ptr() if dropout_p > 0.0 else 0)
 
 
-def _fa_forward_lse(q, k, v, scale, causal):
+def _fa_forward_lse(q, k, v, scale, causal, dropout_p=0.0, seed=None):
     """Forward only: (o, lse), lse the [B,H,S] fp32 natural-log logsumexp
-    of the scaled scores."""
+    of the scaled scores (dropout does not enter it)."""
     B, H, S, D = q.shape
     # O lives in [B,S,H,D] memory so the caller's
     # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
     o = torch.empty((B, S, H, D), dtype=q.dtype,
                     device=q.device).transpose(1, 2)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    _launch_fwd(q, k, v, o, lse, scale, causal=causal)
+    _launch_fwd(q, k, v, o, lse, scale, causal=causal, dropout_p=dropout_p,
+                seed=seed)
     return o, lse
 
 
@@ -102,25 +198,39 @@ def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
     return t.view(B, T, n_head, C // n_head).transpose(1, 2)
 
 
+def _drop_kw(ctx, seed):
+    """Keyword arguments of the launch helpers for ctx's dropout; none at
+    p = 0, so that path calls them exactly as before."""
+    if ctx.dropout_p > 0.0:
+        return {"dropout_p": ctx.dropout_p, "seed": seed}
+    return {}
+
+
 class _FlashAttnFn(torch.autograd.Function):
-    """[B,H,S,D] q, k, v; causal needs S % 128 == 0."""
+    """[B,H,S,D] q, k, v; causal needs S % 128 == 0. seed: the one-element
+    int64 device tensor of the dropout mask, None at dropout_p = 0."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal):
-        o, lse = _fa_forward_lse(q, k, v, scale, causal)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.scale, ctx.causal = scale, causal
+    def forward(ctx, q, k, v, scale, causal, dropout_p=0.0, seed=None):
+        ctx.scale, ctx.causal, ctx.dropout_p = scale, causal, dropout_p
+        o, lse = _fa_forward_lse(q, k, v, scale, causal,
+                                 **_drop_kw(ctx, seed))
+        if dropout_p > 0.0:
+            ctx.save_for_backward(q, k, v, o, lse, seed)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse)
         return o
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, *seed = ctx.saved_tensors
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         dk = torch.empty_like(dq)
         dv = torch.empty_like(dq)
         _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale,
-                    causal=ctx.causal)
-        return dq, dk, dv, None, None
+                    causal=ctx.causal,
+                    **_drop_kw(ctx, seed[0] if seed else None))
+        return dq, dk, dv, None, None, None, None
 
 
 class _FlashAttnQkvFn(torch.autograd.Function):
@@ -129,51 +239,66 @@ class _FlashAttnQkvFn(torch.autograd.Function):
     dq, dk, dv into the three thirds of one [B,T,3C] gradient."""
 
     @staticmethod
-    def forward(ctx, qkv, n_head, scale, causal):
+    def forward(ctx, qkv, n_head, scale, causal, dropout_p=0.0, seed=None):
         B, T, C3 = qkv.shape
         C = C3 // 3
         q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
         y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((B, n_head, T), dtype=torch.float32,
                           device=qkv.device)
-        _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal)
-        ctx.save_for_backward(qkv, y, lse)
         ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
+        ctx.dropout_p = dropout_p
+        _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal,
+                    **_drop_kw(ctx, seed))
+        if dropout_p > 0.0:
+            ctx.save_for_backward(qkv, y, lse, seed)
+        else:
+            ctx.save_for_backward(qkv, y, lse)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        qkv, y, lse = ctx.saved_tensors
+        qkv, y, lse, *seed = ctx.saved_tensors
         H = ctx.n_head
         C = y.shape[2]
         q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
         _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
-                    ctx.scale, causal=ctx.causal)
-        return dqkv, None, None, None
+                    ctx.scale, causal=ctx.causal,
+                    **_drop_kw(ctx, seed[0] if seed else None))
+        return dqkv, None, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     causal: bool = True, dropout_p: float = 0.0,
-                    scale: float = None) -> torch.Tensor:
+                    scale: float = None,
+                    dropout_seed: Optional[torch.Tensor] = None
+                    ) -> torch.Tensor:
     """SDPA drop-in for [B,H,S,D] inputs; runs the hand-written CDNA4
-    kernels when the shape qualifies, torch SDPA otherwise."""
+    kernels when the shape qualifies, torch SDPA otherwise. dropout_seed
+    (kernels only): one-element int64 tensor on the device that fixes the
+    dropout mask; drawn from torch's generator when absent."""
     if fa_supported(q, k, v, causal, dropout_p):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        return _FlashAttnFn.apply(q, k, v, s, causal)
+        seed = (_seed_tensor(dropout_seed, q.device) if dropout_p > 0.0
+                else None)
+        return _FlashAttnFn.apply(q, k, v, s, causal, dropout_p, seed)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
 
 
 def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
                             dropout_p: float = 0.0,
-                            causal: bool = True) -> torch.Tensor:
+                            causal: bool = True,
+                            dropout_seed: Optional[torch.Tensor] = None
+                            ) -> torch.Tensor:
     """split -> head views -> flash_attention -> [B,T,C]."""
     B, T, C3 = qkv.shape
     C = C3 // 3
     q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
-    y = flash_attention(q, k, v, causal=causal, dropout_p=dropout_p)
+    y = flash_attention(q, k, v, causal=causal, dropout_p=dropout_p,
+                        dropout_seed=dropout_seed)
     return y.transpose(1, 2).contiguous().view(B, T, C)
 
 
@@ -189,14 +314,20 @@ def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
 
 def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
                         dropout_p: float = 0.0,
-                        causal: bool = True) -> torch.Tensor:
+                        causal: bool = True,
+                        dropout_seed: Optional[torch.Tensor] = None
+                        ) -> torch.Tensor:
     """Self-attention on the packed projection qkv [B,T,3C] (q, k, v
     thirds, heads contiguous within each); returns [B,T,C]. The qualifying
-    case (bf16, head_dim 64, contiguous, no dropout; T a multiple of 128 when
-    causal, any T >= 1 when not) runs the CDNA4 kernels directly on the
+    case (bf16, head_dim 64, contiguous, dropout_p < 1; T a multiple of 128
+    when causal, any T >= 1 when not) runs the CDNA4 kernels directly on the
     packed layout with no copies; anything else composes
-    ``flash_attention`` from views."""
+    ``flash_attention`` from views. dropout_seed as in ``flash_attention``."""
     if fa_qkv_supported(qkv, n_head, dropout_p, causal):
         scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
-        return _FlashAttnQkvFn.apply(qkv, n_head, scale, causal)
-    return _attention_qkv_composed(qkv, n_head, dropout_p, causal)
+        seed = (_seed_tensor(dropout_seed, qkv.device) if dropout_p > 0.0
+                else None)
+        return _FlashAttnQkvFn.apply(qkv, n_head, scale, causal, dropout_p,
+                                     seed)
+    return _attention_qkv_composed(qkv, n_head, dropout_p, causal,
+                                   dropout_seed)

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG_DIR, "ops", "csrc")
 SOURCES = ["kernels.hip", "engine.hip", "plan.cpp", "lnorm.hip", "ce.hip",
            "attn.hip", "attn_probe.hip", "gelu.hip", "moe.hip",
            "bindings.hip"]
-HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h"]
+HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h", "attn_drop.h"]
 OUT_SO = os.path.join(PKG_DIR, "_core.so")
 STAMP = os.path.join(PKG_DIR, "ops", ".build_stamp")
 

@@ -19,8 +19,18 @@
 // backward splits FA2-style into a dq kernel (q-tile outer) and a dkv
 // kernel (kv-tile outer), both recomputing P from the saved logsumexp.
 //
-// The three kernels are templates on <kCausal, kRagged>. <true,false> is
-// the GPT-2 case. The non-causal mode loops over all ceil(S/64) tiles;
+// The three kernels are templates on <kCausal, kRagged, kDrop>.
+// <true,false,false> is the GPT-2 case. kDrop adds attention dropout on P
+// (mask function in attn_drop.h): the forward zeroes dropped P after the row
+// sum, so the normaliser and lse are those of the undropped scores, and
+// folds 1/(1-p) into the epilogue's 1/rowsum; delta = rowsum(dO*O) needs no
+// change since O carries the dropout; the backward regenerates the mask and
+// forms dS = P * (keep * dP/(1-p) - delta) * scale and
+// dV = (P*keep)^T dO / (1-p), the last factor on the fp32 accumulator. The
+// seed is read from device memory by the kernels, so a captured graph sees
+// the value of each replay. The kDrop=false instantiations are instruction
+// for instruction the kernels without the parameter.
+// The non-causal mode loops over all ceil(S/64) tiles;
 // its kRagged form (S % 128 != 0) clamps the row index of every load to
 // S-1 (so no byte at a row >= S is read and whatever lands in a padding
 // position is finite), masks keys >= S to kNegBig before the running max
@@ -32,11 +42,14 @@
 // kernels (models used stock torch); this op exists to meet BASELINE.json's
 // "hot ops as hand-written MFMA/LDS kernels" requirement.
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
 
+#include "attn_drop.h"
 #include "attn_frag.h"
 
 namespace adapcc {
@@ -74,6 +87,10 @@ struct FaParams {
                        // read by the dkv kernel launched after it
   __bf16 *dq, *dk, *dv;
   TStride dos_, dqs, dks, dvs;
+  // dropout, kDrop instantiations only (both directions)
+  const long* seed;    // device memory: a graph replay sees a fresh value
+  unsigned drop_thr;   // keep iff word >= drop_thr
+  float drop_rp;       // 1/(1-p)
 };
 
 // Row index used for a load: in the ragged mode rows >= S do not exist, so
@@ -150,6 +167,21 @@ __device__ __forceinline__ void st_side(float* side, int buf, unsigned i,
   (side + kSideDelta)[(buf ? 64 : 0) + i] = x.delta;
 }
 
+// Dropout (kDrop instantiations): the mask word of attn_drop.h splits into
+// a per-q and a per-k part. Each kernel computes the part of the axis its
+// lanes own once per lane; the part of the tile's 64 rows of the other axis
+// is computed by threads 0..63 into a double-buffered unsigned[64] pair
+// behind the kernel's other LDS, one tile ahead like the row images. Being
+// computed, not loaded, it is written straight into the buffer the next
+// iteration reads: the barrier that ended the previous iteration retired
+// that buffer's readers.
+template <bool kDrop>
+constexpr int kPartBytes = kDrop ? 2 * 64 * 4 : 0;
+
+__device__ __forceinline__ unsigned* part_buf(unsigned* part, int buf) {
+  return part + (buf ? 64 : 0);
+}
+
 // Four f32 -> four bf16 (round to nearest even), one 8-byte store.
 __device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
                                             float c, float d) {
@@ -179,13 +211,17 @@ __device__ __forceinline__ float ds_elem(float pe, float dp, float delta,
 // Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
 // qt*128 + w*32 .. +31.
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged>
+template <bool kCausal, bool kRagged, bool kDrop>
 __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
-  // 64-row KV tiles, double-buffered: K images, then V images.
-  __shared__ __attribute__((aligned(16))) char smem[4 * kImg];
+  // 64-row KV tiles, double-buffered: K images, then V images (then the
+  // tiles' dropout k parts).
+  __shared__ __attribute__((aligned(16))) char
+      smem[4 * kImg + kPartBytes<kDrop>];
   char* const kimg = smem;
   char* const vimg = smem + 2 * kImg;
+  [[maybe_unused]] unsigned* const kpart =
+      reinterpret_cast<unsigned*>(smem + 4 * kImg);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -227,12 +263,23 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   // 64-row tiles: up to the diagonal (causal) or all of them
   const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
 
+  // dropout: this lane's q part; seed_hi feeds the tiles' k parts
+  [[maybe_unused]] unsigned dqa = 0, seed_hi = 0;
+  if constexpr (kDrop) {
+    const unsigned long sd = (unsigned long)*p.seed;
+    dqa = drop_q_part((unsigned)sd, bh, qrow);
+    seed_hi = (unsigned)(sd >> 32);
+  }
+
   // prologue: stage tile 0
   {
     const long r0 = ld_row<kRagged>((long)srow, p.S);
     const long r1 = ld_row<kRagged>((long)(srow + 32), p.S);
     st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
     st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
+    if constexpr (kDrop)
+      if (threadIdx.x < 64)
+        kpart[threadIdx.x] = drop_k_part(seed_hi, bh, threadIdx.x);
   }
   __syncthreads();
 
@@ -247,6 +294,10 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
       const long kb1 = ld_row<kRagged>(kb + 32, p.S);
       nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
       nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
+      if constexpr (kDrop)
+        if (threadIdx.x < 64)
+          part_buf(kpart, cur ^ 1)[threadIdx.x] =
+              drop_k_part(seed_hi, bh, (t + 1) * 64 + threadIdx.x);
     }
 
 #pragma unroll
@@ -310,6 +361,16 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
       }
       ssum += psum;
 
+      // dropout after the row sum: the normaliser and lse stay those of
+      // the undropped scores; 1/(1-p) goes into the epilogue's inv
+      if constexpr (kDrop) {
+        const unsigned* kp = part_buf(kpart, cur) + half * 32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!drop_keep_parts(dqa, kp[crow(r, hi)], p.drop_thr))
+            pv[r] = 0.f;
+      }
+
       // redistribute P to operand fragments (k blocks 0-15 / 16-31)
       const bf16x8 p0 = pack_frag(&pv[0]);
       const bf16x8 p1 = pack_frag(&pv[8]);
@@ -333,7 +394,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   // epilogue: combine row-sum halves, normalize, store O and lse
   const float stot = ssum + __shfl_xor(ssum, 32, 64);
-  const float inv = 1.f / stot;
+  float inv = 1.f / stot;
+  if constexpr (kDrop) inv = p.drop_rp / stot;
   if (kRagged && qrow >= p.S) return;  // stores only; no barrier follows
   if ((lane >> 5) == 0)
     lseg[qrow] = p.scale * m + __builtin_amdgcn_logf(stot) * kLn2;
@@ -386,13 +448,17 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
   return (pr[0] + pr[1]) + (pr[2] + pr[3]);
 }
 
-template <bool kCausal, bool kRagged>
+template <bool kCausal, bool kRagged, bool kDrop>
 __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
-  // 64-row KV tiles, double-buffered: K images, then V images.
-  __shared__ __attribute__((aligned(16))) char smem[4 * kImg];
+  // 64-row KV tiles, double-buffered: K images, then V images (then the
+  // tiles' dropout k parts).
+  __shared__ __attribute__((aligned(16))) char
+      smem[4 * kImg + kPartBytes<kDrop>];
   char* const kimg = smem;
   char* const vimg = smem + 2 * kImg;
+  [[maybe_unused]] unsigned* const kpart =
+      reinterpret_cast<unsigned*>(smem + 4 * kImg);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -442,11 +508,22 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
   const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
+
+  // dropout: this lane's q part; seed_hi feeds the tiles' k parts
+  [[maybe_unused]] unsigned dqa = 0, seed_hi = 0;
+  if constexpr (kDrop) {
+    const unsigned long sd = (unsigned long)*p.seed;
+    dqa = drop_q_part((unsigned)sd, bh, qrow);
+    seed_hi = (unsigned)(sd >> 32);
+  }
   {
     const long r0 = ld_row32<kRagged>(srow, p.S);
     const long r1 = ld_row32<kRagged>(srow + 32, p.S);
     st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
     st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
+    if constexpr (kDrop)
+      if (threadIdx.x < 64)
+        kpart[threadIdx.x] = drop_k_part(seed_hi, bh, threadIdx.x);
   }
   __syncthreads();
 
@@ -459,6 +536,10 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
       const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, p.S);
       nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
       nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
+      if constexpr (kDrop)
+        if (threadIdx.x < 64)
+          part_buf(kpart, cur ^ 1)[threadIdx.x] =
+              drop_k_part(seed_hi, bh, (t + 1) * 64 + threadIdx.x);
     }
 
 #pragma unroll
@@ -483,19 +564,41 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
 
       // two loops on purpose: the unmasked one carries no compare
       float ds[16];
-      if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
+      // dropout: the MFMA gave dP of the dropped, rescaled P; the dP that
+      // dS wants is keep * that / (1-p)
+      [[maybe_unused]] const unsigned* kp =
+          part_buf(kpart, cur) + half * 32;
+      auto dpk = [&](int r) {
+        if constexpr (kDrop)
+          return drop_keep_parts(dqa, kp[crow(r, hi)], p.drop_thr)
+                     ? dp[r] * p.drop_rp
+                     : 0.f;
+        else
+          return dp[r];
+      };
+      if (kDrop) {
+        // one loop: beside the mask word the compare is cheap, and the
+        // second copy of the loop costs registers (scratch at 3 waves/SIMD)
+        const int lim = kCausal ? qrow : kRagged ? p.S - 1 : 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kglob = kbase + crow(r, hi);
+          const float pe = kglob > lim ? 0.f : p_elem(s[r], c1, lse2);
+          ds[r] = ds_elem(pe, dpk(r), dvq, p.scale);
+        }
+      } else if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
           const float pe = (kCausal ? kglob > qrow : kglob >= p.S)
                                ? 0.f
                                : p_elem(s[r], c1, lse2);
-          ds[r] = ds_elem(pe, dp[r], dvq, p.scale);
+          ds[r] = ds_elem(pe, dpk(r), dvq, p.scale);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          ds[r] = ds_elem(p_elem(s[r], c1, lse2), dp[r], dvq, p.scale);
+          ds[r] = ds_elem(p_elem(s[r], c1, lse2), dpk(r), dvq, p.scale);
       }
       const bf16x8 d0 = pack_frag(&ds[0]);
       const bf16x8 d1 = pack_frag(&ds[8]);
@@ -536,16 +639,19 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
 //   dV += P^T·dO   (A=packed P^T, B=dO^T tr frags)
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged>
+template <bool kCausal, bool kRagged, bool kDrop>
 __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
   // 64-row q tiles, double-buffered: Q images, then dO images, then the
-  // lse2/delta side tile; the epilogue reuses [0,32K) as per-wave f32
-  // scratch for the coalesced dV/dK stores.
-  __shared__ __attribute__((aligned(16))) char smem[4 * kImg + 1024];
+  // lse2/delta side tile (then the tiles' dropout q parts); the epilogue
+  // reuses [0,32K) as per-wave f32 scratch for the coalesced dV/dK stores.
+  __shared__ __attribute__((aligned(16))) char
+      smem[4 * kImg + 1024 + kPartBytes<kDrop>];
   char* const qimg = smem;
   char* const doimg = smem + 2 * kImg;
   float* const side = reinterpret_cast<float*>(smem + 4 * kImg);
+  [[maybe_unused]] unsigned* const qpart =
+      reinterpret_cast<unsigned*>(smem + 4 * kImg + 1024);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -586,6 +692,14 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   const int t0 = kCausal ? kt : 0;          // first 64-row q tile
   const int n64 = (p.S + 63) / 64;
 
+  // dropout: this lane's k part; seed_lo feeds the tiles' q parts
+  [[maybe_unused]] unsigned dkb = 0, seed_lo = 0;
+  if constexpr (kDrop) {
+    const unsigned long sd = (unsigned long)*p.seed;
+    seed_lo = (unsigned)sd;
+    dkb = drop_k_part((unsigned)(sd >> 32), bh, krow);
+  }
+
   // stage q/dO tile t0 and its side tile
   {
     const int qb0 = t0 * 64;
@@ -596,6 +710,8 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
     if (threadIdx.x < 64) {
       const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, p.S);
       st_side(side, 0, threadIdx.x, ld_side(lseg, deltag, rq));
+      if constexpr (kDrop)
+        qpart[threadIdx.x] = drop_q_part(seed_lo, bh, qb0 + threadIdx.x);
     }
   }
   __syncthreads();
@@ -614,6 +730,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
       if (threadIdx.x < 64) {
         const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, p.S);
         ns = ld_side(lseg, deltag, rq);
+        if constexpr (kDrop)
+          part_buf(qpart, cur ^ 1)[threadIdx.x] =
+              drop_q_part(seed_lo, bh, qb1 + threadIdx.x);
       }
     }
 
@@ -642,6 +761,16 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 
       // two loops on purpose: the unmasked one carries no compare
       float pv[16], ds[16];
+      // dropout: dS takes the undropped P and keep * dP / (1-p)
+      [[maybe_unused]] bool keep[16];
+      if constexpr (kDrop) {
+        const unsigned* qp = part_buf(qpart, cur) + half * 32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          keep[r] = drop_keep_parts(qp[crow(r, hi)], dkb, p.drop_thr);
+          dp[r] = keep[r] ? dp[r] * p.drop_rp : 0.f;
+        }
+      }
       if (kCausal ? qbase < kbb + 31 : kRagged && qbase + 31 >= p.S) {
         // diagonal: mask q < k; ragged: mask the q rows past S-1
 #pragma unroll
@@ -658,6 +787,13 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
           pv[r] = p_elem(sacc[r], c1, lsec[crow(r, hi)]);
           ds[r] = ds_elem(pv[r], dp[r], dc[crow(r, hi)], p.scale);
         }
+      }
+      // dV takes the dropped P; its 1/(1-p) goes onto the accumulator in
+      // the epilogue
+      if constexpr (kDrop) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!keep[r]) pv[r] = 0.f;
       }
       const bf16x8 p0 = pack_frag(&pv[0]);
       const bf16x8 p1 = pack_frag(&pv[8]);
@@ -694,10 +830,18 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   for (int t = 0; t < 2; ++t) {  // 0: dV, 1: dK
     const f32x16& a0 = t ? dkacc0 : dvacc0;
     const f32x16& a1 = t ? dkacc1 : dvacc1;
+    if (kDrop && t == 0) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      scratch[crow(r, hi) * 64 + (lane & 31)] = a0[r];
-      scratch[crow(r, hi) * 64 + 32 + (lane & 31)] = a1[r];
+      for (int r = 0; r < 16; ++r) {
+        scratch[crow(r, hi) * 64 + (lane & 31)] = a0[r] * p.drop_rp;
+        scratch[crow(r, hi) * 64 + 32 + (lane & 31)] = a1[r] * p.drop_rp;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        scratch[crow(r, hi) * 64 + (lane & 31)] = a0[r];
+        scratch[crow(r, hi) * 64 + 32 + (lane & 31)] = a1[r];
+      }
     }
     __builtin_amdgcn_s_waitcnt(0);  // drain LDS writes (wave-local reuse)
     __bf16* outg = (t ? dkg : dvg);
@@ -716,10 +860,46 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 }
 
 // ---------------------------------------------------------------------------
+// The dropout mask itself, keep(seed, bh, q, k) as [B*H][S][S] bytes: the
+// bridge between the three kernels above and the torch replica.
+// Grid (ceil(S*S/256), B*H).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fa_dropout_mask_kernel(
+    uint8_t* out, const long* seed, int S, unsigned thr) {
+  const long n = (long)S * S;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned bh = blockIdx.y;
+  out[bh * n + i] =
+      drop_keep(*seed, bh, (unsigned)(i / S), (unsigned)(i % S), thr);
+}
+
+// ---------------------------------------------------------------------------
 // Host side.
 // ---------------------------------------------------------------------------
 TStride stride_at(const long* s, int i) {
   return {s[3 * i], s[3 * i + 1], s[3 * i + 2]};
+}
+
+// thr = clamp(round(p * 2^32), 1, 2^32 - 1), ties to even like Python's
+// round(): the replica computes the same number.
+unsigned drop_threshold(double p) {
+  const double t = std::nearbyint(p * 4294967296.0);
+  return (unsigned)std::min(std::max(t, 1.0), 4294967295.0);
+}
+
+void check_drop(const char* name, double p, const long* seed) {
+  if (!(p >= 0.0 && p < 1.0))
+    throw std::runtime_error(std::string(name) + ": need 0 <= dropout_p < 1");
+  if (p > 0.0 && seed == nullptr)
+    throw std::runtime_error(std::string(name) +
+                             ": dropout needs a device seed");
+}
+
+void set_drop(FaParams& p, double dropout_p, const long* seed) {
+  p.seed = seed;
+  p.drop_thr = drop_threshold(dropout_p);
+  p.drop_rp = (float)(1.0 / (1.0 - dropout_p));
 }
 
 void check_len(const char* name, int S, bool causal) {
@@ -729,15 +909,22 @@ void check_len(const char* name, int S, bool causal) {
                              ": causal needs S % 128 == 0");
 }
 
-// Calls f(kCausal, kRagged) with the mode as two std::bool_constant values.
+// Calls f(kCausal, kRagged, kDrop) with the mode as three
+// std::bool_constant values.
 template <typename F>
-void with_mode(bool causal, int S, F&& f) {
-  if (causal)
-    f(std::true_type{}, std::false_type{});
-  else if (S % kQT == 0)
-    f(std::false_type{}, std::false_type{});
+void with_mode(bool causal, int S, bool drop, F&& f) {
+  auto g = [&](auto d) {
+    if (causal)
+      f(std::true_type{}, std::false_type{}, d);
+    else if (S % kQT == 0)
+      f(std::false_type{}, std::false_type{}, d);
+    else
+      f(std::false_type{}, std::true_type{}, d);
+  };
+  if (drop)
+    g(std::true_type{});
   else
-    f(std::false_type{}, std::true_type{});
+    g(std::false_type{});
 }
 
 // The part of the parameter block that both directions fill. strides: 3 per
@@ -764,17 +951,25 @@ FaParams fwd_params(const void* q, const void* k, const void* v, void* o,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Host launchers (bound in bindings.hip).
+// Host launchers (bound in bindings.hip). dropout_p == 0 launches the
+// kDrop=false instantiations, which are the kernels without dropout, and
+// never touches seed; dropout_p > 0 reads the 64-bit seed at `seed` (device
+// memory) when the kernel runs.
 // ---------------------------------------------------------------------------
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
-                float scale, hipStream_t stream, bool causal) {
+                float scale, hipStream_t stream, bool causal,
+                double dropout_p, const long* seed) {
   check_len("fa_forward", S, causal);
-  const FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
+  check_drop("fa_forward", dropout_p, seed);
+  FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
+  set_drop(p, dropout_p, seed);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  with_mode(causal, S, [&](auto c, auto r) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value;
-    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR>), grid, dim3(256), 0, stream, p);
+  with_mode(causal, S, dropout_p > 0.0, [&](auto c, auto r, auto d) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                   kD = decltype(d)::value;
+    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR, kD>), grid, dim3(256), 0,
+                       stream, p);
   });
 }
 
@@ -783,10 +978,13 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
-                 float scale, hipStream_t stream, bool causal) {
+                 float scale, hipStream_t stream, bool causal,
+                 double dropout_p, const long* seed) {
   check_len("fa_backward", S, causal);
+  check_drop("fa_backward", dropout_p, seed);
   FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
                           const_cast<float*>(lse), H, S, strides, scale);
+  set_drop(p, dropout_p, seed);
   p.dout = (const __bf16*)do_;
   p.delta = delta;
   p.dq = (__bf16*)dq;
@@ -797,13 +995,29 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
   p.dks = stride_at(strides, 6);
   p.dvs = stride_at(strides, 7);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  with_mode(causal, S, [&](auto c, auto r) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value;
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR>), grid, dim3(256), 0, stream,
-                       p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR>), grid, dim3(256), 0, stream,
-                       p);
+  with_mode(causal, S, dropout_p > 0.0, [&](auto c, auto r, auto d) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                   kD = decltype(d)::value;
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR, kD>), grid, dim3(256), 0,
+                       stream, p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR, kD>), grid, dim3(256), 0,
+                       stream, p);
   });
 }
 
+// out: [B,H,S,S] bytes, 1 where the element is kept.
+void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
+                     double dropout_p, hipStream_t stream) {
+  if (S < 1 || B < 1 || H < 1)
+    throw std::runtime_error("fa_dropout_mask: empty shape");
+  if (seed == nullptr)
+    throw std::runtime_error("fa_dropout_mask: needs a device seed");
+  check_drop("fa_dropout_mask", dropout_p, seed);
+  const long n = (long)S * S;
+  const dim3 grid((unsigned)((n + 255) / 256), B * H);
+  hipLaunchKernelGGL(fa_dropout_mask_kernel, grid, dim3(256), 0, stream, out,
+                     seed, S, drop_threshold(dropout_p));
+}
+
 }  // namespace adapcc
+

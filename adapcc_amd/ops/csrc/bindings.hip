@@ -88,11 +88,15 @@ void ce_backward(int dtype, const void* logits, const void* targets,
                  long rows, long cols, long ignore_index, hipStream_t stream);
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
-                float scale, hipStream_t stream, bool causal);
+                float scale, hipStream_t stream, bool causal,
+                double dropout_p, const long* seed);
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
-                 float scale, hipStream_t stream, bool causal);
+                 float scale, hipStream_t stream, bool causal,
+                 double dropout_p, const long* seed);
+void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
+                     double dropout_p, hipStream_t stream);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -195,26 +199,29 @@ PYBIND11_MODULE(_core, m) {
   m.def("fa_fwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            int B, int H, int S, const std::vector<long>& strides, float scale,
-           uintptr_t stream, bool causal) {
+           uintptr_t stream, bool causal, double dropout_p, uintptr_t seed) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_fwd: need 12 strides");
           adapcc::fa_forward((const void*)q, (const void*)k, (const void*)v,
                              (void*)o, (float*)lse, B, H, S, strides.data(),
                              scale, reinterpret_cast<hipStream_t>(stream),
-                             causal);
+                             causal, dropout_p, (const long*)seed);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
-        // causal=False: non-causal self-attention, any S >= 1
+        // causal=False: non-causal self-attention, any S >= 1.
+        // dropout_p > 0: seed is the address of one int64 in device memory
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("S"),
         py::arg("strides"), py::arg("scale"), py::arg("stream"),
-        py::arg("causal") = true);
+        py::arg("causal") = true, py::arg("dropout_p") = 0.0,
+        py::arg("seed") = 0);
   m.def("fa_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, int B, int H, int S, const std::vector<long>& strides,
-           float scale, uintptr_t stream, bool causal) {
+           float scale, uintptr_t stream, bool causal, double dropout_p,
+           uintptr_t seed) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_bwd: need 24 strides");
           adapcc::fa_backward((const void*)q, (const void*)k, (const void*)v,
@@ -222,7 +229,7 @@ PYBIND11_MODULE(_core, m) {
                               (const float*)lse, (float*)delta, (void*)dq,
                               (void*)dk, (void*)dv, B, H, S, strides.data(),
                               scale, reinterpret_cast<hipStream_t>(stream),
-                              causal);
+                              causal, dropout_p, (const long*)seed);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -230,7 +237,20 @@ PYBIND11_MODULE(_core, m) {
         py::arg("dout"), py::arg("lse"), py::arg("delta"), py::arg("dq"),
         py::arg("dk"), py::arg("dv"), py::arg("B"), py::arg("H"),
         py::arg("S"), py::arg("strides"), py::arg("scale"),
-        py::arg("stream"), py::arg("causal") = true);
+        py::arg("stream"), py::arg("causal") = true,
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
+  // out: [B,H,S,S] uint8, 1 where the attention kernels keep the element
+  m.def("fa_dropout_mask",
+        [](uintptr_t out, uintptr_t seed, int B, int H, int S,
+           double dropout_p, uintptr_t stream) {
+          adapcc::fa_dropout_mask((uint8_t*)out, (const long*)seed, B, H, S,
+                                  dropout_p,
+                                  reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("out"), py::arg("seed"), py::arg("B"), py::arg("H"),
+        py::arg("S"), py::arg("dropout_p"), py::arg("stream"));
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

@@ -34,6 +34,10 @@ def main():
     p.add_argument("--lr", type=float, default=3e-4)
     p.add_argument("--entry_point", type=int, default=-1)
     p.add_argument("--relay", action="store_true")
+    p.add_argument("--dropout", type=float, default=0.0,
+                   help="attention, residual and embedding dropout (the "
+                        "reference's GPT2Config default is 0.1); attention "
+                        "dropout runs inside the flash attention kernels")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -48,6 +52,7 @@ def main():
         dist.init_process_group("nccl" if use_cuda else "gloo")
 
     cfg = getattr(GPT2Config, args.model)()
+    cfg.dropout = args.dropout
     torch.manual_seed(1)
     model = GPT2(cfg).to(device)
     AdapCC.init(CommArgs(entry_point=args.entry_point, relay=args.relay),

@@ -27,6 +27,10 @@ def main():
     p.add_argument("--bf16", action="store_true",
                    help="forward and loss under autocast bf16 (reaches the "
                         "flash attention kernels)")
+    p.add_argument("--attn-dropout", type=float, default=0.0,
+                   help="dropout on the attention probabilities (the "
+                        "reference trains with 0.1); with --bf16 it runs "
+                        "inside the flash attention kernels")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -41,6 +45,7 @@ def main():
         dist.init_process_group("nccl" if use_cuda else "gloo")
 
     cfg = ViTConfig.tiny() if args.tiny else ViTConfig.base()
+    cfg.attn_dropout = args.attn_dropout
     torch.manual_seed(3)
     model = ViT(cfg).to(device)
     AdapCC.init(CommArgs(entry_point=-1), local_rank, rank, world)
