@@ -28,6 +28,9 @@ class GPT2Config:
     n_layer: int = 12
     n_head: int = 12
     dropout: float = 0.0
+    # dropout on each sublayer's output before it joins the residual stream
+    # (transformers' resid_pdrop), fused with the add and the next LayerNorm
+    resid_dropout: float = 0.0
 
     @classmethod
     def small(cls) -> "GPT2Config":
@@ -87,6 +90,23 @@ class Block(nn.Module):
         x = x + self.mlp(self.ln_2(x))
         return x
 
+    def forward_resid_dropout(self, x: torch.Tensor, y: torch.Tensor,
+                              next_ln: nn.LayerNorm, p: float, site: int):
+        """The block with residual dropout p. x: the residual stream, y =
+        ln_1(x), already computed where x was. Each sublayer output goes
+        through one fused dropout + add + LayerNorm: the attention's with
+        ln_2, the MLP's with next_ln (the next block's ln_1, or ln_f).
+        Returns the new stream and next_ln of it; uses mask sites site and
+        site + 1."""
+        from ..ops.fused import fused_dropout_add_layer_norm
+
+        x, y = fused_dropout_add_layer_norm(
+            self.attn(y), x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps,
+            dropout_p=p, site=site)
+        return fused_dropout_add_layer_norm(
+            self.mlp(y), x, next_ln.weight, next_ln.bias, next_ln.eps,
+            dropout_p=p, site=site + 1)
+
 
 class GPT2(nn.Module):
     def __init__(self, cfg: GPT2Config):
@@ -124,9 +144,19 @@ class GPT2(nn.Module):
         B, T = idx.shape
         pos = torch.arange(T, device=idx.device)
         x = self.drop(self.wte(idx) + self.wpe(pos))
-        for block in self.h:
-            x = block(x)
-        x = self.ln_f(x)
+        if self.training and self.cfg.resid_dropout > 0.0:
+            # every LayerNorm but the first runs fused with the add (and
+            # dropout) in front of it: 2 * n_layer calls, one site each
+            lns = [b.ln_1 for b in self.h[1:]] + [self.ln_f]
+            y = self.h[0].ln_1(x)
+            for i, block in enumerate(self.h):
+                x, y = block.forward_resid_dropout(
+                    x, y, lns[i], self.cfg.resid_dropout, site=2 * i)
+            x = y
+        else:
+            for block in self.h:
+                x = block(x)
+            x = self.ln_f(x)
         logits = self.lm_head(x)
         loss = None
         if targets is not None:

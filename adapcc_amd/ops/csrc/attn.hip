@@ -950,6 +950,9 @@ FaParams fwd_params(const void* q, const void* k, const void* v, void* o,
 
 }  // namespace
 
+// drop_threshold for the other users of attn_drop.h's mask (lnorm.hip).
+unsigned fa_drop_threshold(double p) { return drop_threshold(p); }
+
 // ---------------------------------------------------------------------------
 // Host launchers (bound in bindings.hip). dropout_p == 0 launches the
 // kDrop=false instantiations, which are the kernels without dropout, and

@@ -80,6 +80,18 @@ void ln_backward(int dtype, const void* dy, const void* x, const void* w,
                  const float* mean, const float* rstd, void* dx,
                  float* ws_gamma, float* ws_beta, long rows, long cols,
                  int nblocks, hipStream_t stream);
+void ln_dropadd_forward(int dtype, const void* h, const void* res,
+                        const void* w, const void* b, void* x_new, void* y,
+                        float* mean, float* rstd, long rows, long cols,
+                        float eps, double dropout_p, const long* seed,
+                        unsigned site, hipStream_t stream);
+void ln_dropadd_backward(int dtype, const void* dy, const void* dx_new,
+                         const void* x_new, const void* w, const float* mean,
+                         const float* rstd, void* dres, void* dh,
+                         float* ws_gamma, float* ws_beta, long rows,
+                         long cols, int nblocks, double dropout_p,
+                         const long* seed, unsigned site,
+                         hipStream_t stream);
 void ce_forward(int dtype, const void* logits, const void* targets,
                 float* loss, float* lse, long rows, long cols,
                 long ignore_index, hipStream_t stream);
@@ -171,6 +183,49 @@ PYBIND11_MODULE(_core, m) {
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
+  // x_new = residual + dropout(h), y = LN(x_new). dropout_p > 0: seed is
+  // the address of one int64 in device memory, as in fa_fwd.
+  m.def("ln_dropadd_fwd",
+        [](int dtype, uintptr_t h, uintptr_t res, uintptr_t w, uintptr_t b,
+           uintptr_t x_new, uintptr_t y, uintptr_t mean, uintptr_t rstd,
+           long rows, long cols, float eps, uintptr_t stream,
+           double dropout_p, uintptr_t seed, unsigned site) {
+          adapcc::ln_dropadd_forward(
+              dtype, (const void*)h, (const void*)res, (const void*)w,
+              (const void*)b, (void*)x_new, (void*)y, (float*)mean,
+              (float*)rstd, rows, cols, eps, dropout_p, (const long*)seed,
+              site, reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("dtype"), py::arg("h"), py::arg("res"), py::arg("w"),
+        py::arg("b"), py::arg("x_new"), py::arg("y"), py::arg("mean"),
+        py::arg("rstd"), py::arg("rows"), py::arg("cols"), py::arg("eps"),
+        py::arg("stream"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
+        py::arg("site") = 0);
+  // dx_new = 0: no gradient reaches x_new directly. dh is written only at
+  // dropout_p > 0 (at 0 it equals dres).
+  m.def("ln_dropadd_bwd",
+        [](int dtype, uintptr_t dy, uintptr_t dx_new, uintptr_t x_new,
+           uintptr_t w, uintptr_t mean, uintptr_t rstd, uintptr_t dres,
+           uintptr_t dh, uintptr_t wsg, uintptr_t wsb, long rows, long cols,
+           int nblocks, uintptr_t stream, double dropout_p, uintptr_t seed,
+           unsigned site) {
+          adapcc::ln_dropadd_backward(
+              dtype, (const void*)dy, (const void*)dx_new,
+              (const void*)x_new, (const void*)w, (const float*)mean,
+              (const float*)rstd, (void*)dres, (void*)dh, (float*)wsg,
+              (float*)wsb, rows, cols, nblocks, dropout_p, (const long*)seed,
+              site, reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("dtype"), py::arg("dy"), py::arg("dx_new"), py::arg("x_new"),
+        py::arg("w"), py::arg("mean"), py::arg("rstd"), py::arg("dres"),
+        py::arg("dh"), py::arg("wsg"), py::arg("wsb"), py::arg("rows"),
+        py::arg("cols"), py::arg("nblocks"), py::arg("stream"),
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
+        py::arg("site") = 0);
 
   m.def("ce_fwd",
         [](int dtype, uintptr_t logits, uintptr_t targets, uintptr_t loss,

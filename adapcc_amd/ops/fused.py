@@ -1,7 +1,17 @@
 """Fused CDNA4 op wrappers (autograd integration for the hand-written HIP
-kernels in csrc/lnorm.hip)."""
+kernels in csrc/lnorm.hip, csrc/ce.hip and csrc/gelu.hip).
+
+``fused_dropout_add_layer_norm`` is the pre-norm residual step
+``x_new = residual + dropout(h); y = LayerNorm(x_new)`` in one kernel each
+way. Its mask is the attention kernels' keep(seed, site, row, col)
+(csrc/attn_drop.h) over the flattened rows, regenerated in the backward and
+never stored; the seed is attention's too: one int64 on the device, drawn
+from torch's generator per call or passed as ``dropout_seed``.
+``dropout_add_keep_mask_reference`` is that mask in torch integer ops."""
 
 from __future__ import annotations
+
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -185,3 +195,186 @@ class FusedLayerNorm(nn.LayerNorm):
             return _FusedLayerNormFn.apply(x, self.weight, self.bias,
                                            self.eps)
         return super().forward(x)
+
+
+# ---------------------------------------------------------------------------
+# Residual dropout + add + LayerNorm
+# ---------------------------------------------------------------------------
+def dropout_add_keep_mask_reference(seed, rows: int, cols: int, p: float,
+                                    site: int = 0) -> torch.Tensor:
+    """The ln_dropadd kernels' keep(seed, site, row, col) as a [rows, cols]
+    bool tensor on the CPU, in torch integer ops: the rectangular form of
+    ``attention.dropout_keep_mask_reference`` with the plane index as the
+    call site (csrc/attn_drop.h is the definition). seed: int or one-element
+    int64 tensor."""
+    from .attention import _M32, _drop_threshold, _fmix
+
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed_lo, seed_hi = seed & _M32, seed >> 32
+    site = int(site) & _M32
+    r = torch.arange(rows, dtype=torch.int64).view(-1, 1)
+    c = torch.arange(cols, dtype=torch.int64).view(1, -1)
+    a = _fmix((seed_lo + site * 0x9E3779B1 + r * 0x85EBCA77) & _M32)
+    b = _fmix(((seed_hi ^ ((site * 0xC2B2AE3D) & _M32))
+               + c * 0x27D4EB2F) & _M32)
+    x = (a + b) & _M32
+    x = (x * 0x2C1B3C6D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x297A2D39) & _M32
+    x = x ^ (x >> 15)
+    return x >= _drop_threshold(p)
+
+
+def _dropadd_fusable(h: torch.Tensor, residual: torch.Tensor,
+                     weight: torch.Tensor, bias: torch.Tensor) -> bool:
+    """What the ln_dropadd kernels take: GPU, no autocast, one dtype for
+    all four, a supported width, 1 <= rows < 2^32 (the mask's row word)."""
+    if not h.is_cuda or torch.is_autocast_enabled():
+        return False
+    if weight is None or bias is None or h.dim() < 1:
+        return False
+    if not (h.dtype == residual.dtype == weight.dtype == bias.dtype):
+        return False
+    if not (h.device == residual.device == weight.device == bias.device):
+        return False
+    cols = h.shape[-1]
+    if weight.shape != (cols,) or bias.shape != (cols,) or cols == 0:
+        return False
+    if not 1 <= h.numel() // cols < 2 ** 32:
+        return False
+    return ln_fusable(cols, h.dtype)
+
+
+def _launch_dropadd_fwd(h, residual, weight, bias, x_new, y, mean, rstd,
+                        eps, dropout_p, seed, site):
+    cols = h.shape[-1]
+    stream = torch.cuda.current_stream(h.device).cuda_stream
+    _core().ln_dropadd_fwd(
+        _DT[h.dtype], h.data_ptr(), residual.data_ptr(), weight.data_ptr(),
+        bias.data_ptr(), x_new.data_ptr(), y.data_ptr(), mean.data_ptr(),
+        rstd.data_ptr(), h.numel() // cols, cols, eps, stream, dropout_p,
+        seed.data_ptr() if dropout_p > 0.0 else 0, site)
+
+
+def _launch_dropadd_bwd(dy, dx_new, x_new, weight, mean, rstd, dres, dh,
+                        wsg, wsb, nblocks, dropout_p, seed, site):
+    """dx_new: None when no gradient reaches x_new directly; dh: None at
+    dropout_p = 0, where it equals dres."""
+    cols = x_new.shape[-1]
+    stream = torch.cuda.current_stream(x_new.device).cuda_stream
+    _core().ln_dropadd_bwd(
+        _DT[x_new.dtype], dy.data_ptr(),
+        dx_new.data_ptr() if dx_new is not None else 0, x_new.data_ptr(),
+        weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dres.data_ptr(),
+        dh.data_ptr() if dh is not None else 0, wsg.data_ptr(),
+        wsb.data_ptr(), x_new.numel() // cols, cols, nblocks, stream,
+        dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0, site)
+
+
+class _DropoutAddLayerNormFn(torch.autograd.Function):
+    """(x_new, y) of the fused step. Saves x_new, weight, the row
+    statistics and, with dropout, the seed: neither h nor a mask."""
+
+    @staticmethod
+    def forward(ctx, h, residual, weight, bias, eps, dropout_p, seed, site):
+        hc, rc = h.contiguous(), residual.contiguous()
+        cols = rc.shape[-1]
+        rows = rc.numel() // cols
+        x_new = torch.empty_like(rc)
+        y = torch.empty_like(rc)
+        mean = torch.empty(rows, dtype=torch.float32, device=rc.device)
+        rstd = torch.empty_like(mean)
+        _launch_dropadd_fwd(hc, rc, weight, bias, x_new, y, mean, rstd, eps,
+                            dropout_p, seed, site)
+        ctx.dropout_p, ctx.site = dropout_p, site
+        if dropout_p > 0.0:
+            ctx.save_for_backward(x_new, weight, mean, rstd, seed)
+        else:
+            ctx.save_for_backward(x_new, weight, mean, rstd)
+        # an output nobody differentiates arrives as None, not as zeros
+        ctx.set_materialize_grads(False)
+        return x_new, y
+
+    @staticmethod
+    def backward(ctx, dx_new, dy):
+        x_new, weight, mean, rstd, *seed = ctx.saved_tensors
+        if dx_new is None and dy is None:
+            return (None,) * 8
+        cols = x_new.shape[-1]
+        rows = x_new.numel() // cols
+        # only x_new is used: the LN branch contributes exact zeros
+        dyc = dy.contiguous() if dy is not None else torch.zeros_like(x_new)
+        dxc = dx_new.contiguous() if dx_new is not None else None
+        dres = torch.empty_like(x_new)
+        dh = torch.empty_like(x_new) if ctx.dropout_p > 0.0 else None
+        nblocks = max(1, min(1024, (rows + 3) // 4))
+        nslots = nblocks * 4  # one partial per wave, as in ln_bwd
+        ws = torch.empty(2 * nslots * cols, dtype=torch.float32,
+                         device=x_new.device)
+        wsg = ws[: nslots * cols]
+        wsb = ws[nslots * cols:]
+        _launch_dropadd_bwd(dyc, dxc, x_new, weight, mean, rstd, dres, dh,
+                            wsg, wsb, nblocks, ctx.dropout_p,
+                            seed[0] if seed else None, ctx.site)
+        dgamma = wsg.view(nslots, cols).sum(0).to(weight.dtype)
+        dbeta = wsb.view(nslots, cols).sum(0).to(weight.dtype)
+        return (dh if dh is not None else dres, dres, dgamma, dbeta,
+                None, None, None, None)
+
+
+def _dropout_add_layer_norm_composed(h, residual, weight, bias, eps,
+                                     dropout_p, dropout_seed, site):
+    """The same step in plain torch. With dropout it applies the replica
+    mask in fp32 with one rounding, like the kernel, so an explicit seed
+    drops the same elements on every path (reading the seed for the replica
+    is a host sync on the GPU)."""
+    from .attention import _seed_tensor
+
+    cols = h.shape[-1]
+    if dropout_p > 0.0:
+        seed = _seed_tensor(dropout_seed, h.device)
+        keep = dropout_add_keep_mask_reference(
+            seed, h.numel() // max(cols, 1), cols, dropout_p, site)
+        keep = keep.view(h.shape).to(h.device)
+        rf = residual.float()
+        x_new = torch.where(keep, rf + h.float() * (1.0 / (1.0 - dropout_p)),
+                            rf).to(torch.result_type(h, residual))
+    else:
+        x_new = residual + h
+    y = torch.nn.functional.layer_norm(x_new, (cols,), weight, bias, eps)
+    return x_new, y
+
+
+def fused_dropout_add_layer_norm(h: torch.Tensor, residual: torch.Tensor,
+                                 weight: torch.Tensor, bias: torch.Tensor,
+                                 eps: float = 1e-5, dropout_p: float = 0.0,
+                                 dropout_seed: Optional[torch.Tensor] = None,
+                                 site: int = 0):
+    """x_new = residual + dropout(h, dropout_p); y = LayerNorm(x_new) over
+    the last dimension. Returns (x_new, y), both differentiable. In fp32 per
+    element, x_new = round(residual + h / (1 - p)) where kept and residual
+    itself where dropped; y is exactly ``FusedLayerNorm`` of x_new.
+
+    GPU tensors of one dtype (f32, f16, bf16) at a width ``ln_fusable``
+    takes run the HIP kernels; anything else (CPU, autocast, mixed dtypes,
+    other widths) composes the same step in torch. dropout_seed: one-element
+    int64 tensor on the inputs' device fixing the mask, drawn from torch's
+    generator when absent (not at dropout_p = 0). site: a uint32 naming the
+    call site, so calls sharing one seed get independent masks."""
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError("fused_dropout_add_layer_norm: need 0 <= dropout_p "
+                         "< 1")
+    if not 0 <= site < 2 ** 32:
+        raise ValueError("fused_dropout_add_layer_norm: site is a uint32")
+    if h.shape != residual.shape:
+        raise ValueError("fused_dropout_add_layer_norm: h and residual "
+                         "differ in shape")
+    if _dropadd_fusable(h, residual, weight, bias):
+        from .attention import _seed_tensor
+
+        seed = (_seed_tensor(dropout_seed, h.device) if dropout_p > 0.0
+                else None)
+        return _DropoutAddLayerNormFn.apply(h, residual, weight, bias, eps,
+                                            dropout_p, seed, site)
+    return _dropout_add_layer_norm_composed(h, residual, weight, bias, eps,
+                                            dropout_p, dropout_seed, site)

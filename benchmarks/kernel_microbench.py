@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-bench driver for the custom CDNA4 kernels (used under rocprofv3
---pmc for counter evidence): fused LayerNorm fwd/bwd and the multi-source
-reduction at the GPT-2 shapes."""
+--pmc for counter evidence): fused LayerNorm fwd/bwd, fused residual dropout
++ add + LayerNorm, cross-entropy and the multi-source reduction at the GPT-2
+shapes."""
 
 import os
 import sys
@@ -27,6 +28,18 @@ def main():
         y = ln(x)
         y.backward(g)
         x.grad = None
+    torch.cuda.synchronize()
+
+    # residual dropout + add + LayerNorm at the same shape (the
+    # <.., true, true> instantiations of the two LN kernels)
+    from adapcc_amd.ops.fused import fused_dropout_add_layer_norm
+    h = torch.randn_like(x, requires_grad=True)
+    gx = torch.randn_like(x)
+    for _ in range(20):
+        x_new, y = fused_dropout_add_layer_norm(h, x, ln.weight, ln.bias,
+                                                ln.eps, dropout_p=0.1)
+        torch.autograd.backward((x_new, y), (gx, g))
+        x.grad = h.grad = None
     torch.cuda.synchronize()
 
     # fused cross-entropy at the GPT-2 logits shape

@@ -37,7 +37,8 @@ def main():
     p.add_argument("--dropout", type=float, default=0.0,
                    help="attention, residual and embedding dropout (the "
                         "reference's GPT2Config default is 0.1); attention "
-                        "dropout runs inside the flash attention kernels")
+                        "dropout runs inside the flash attention kernels, "
+                        "residual dropout inside the fused add+LayerNorm")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -53,6 +54,7 @@ def main():
 
     cfg = getattr(GPT2Config, args.model)()
     cfg.dropout = args.dropout
+    cfg.resid_dropout = args.dropout
     torch.manual_seed(1)
     model = GPT2(cfg).to(device)
     AdapCC.init(CommArgs(entry_point=args.entry_point, relay=args.relay),
