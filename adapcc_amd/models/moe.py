@@ -8,6 +8,13 @@ Capacity-based top-1 routing (GShard-style): per expert, up to
 ``capacity = ceil(tokens/num_experts * capacity_factor)`` tokens are
 dispatched, the rest fall through on the residual path. Equal-size buffers
 make the exchange a single equal-split all-to-all in each direction.
+
+``top_k=2`` (fastmoe's default, the GShard and Mixtral configuration) sends
+every token to its two best experts, first choices having priority on the
+capacity ``ceil(top_k * tokens/num_experts * capacity_factor)``, and
+``balance_loss=True`` leaves the Switch/GShard load-balancing loss of the
+last forward in ``MoEMLP.aux_loss``; both go through
+``ops.moe.moe_route_topk`` and leave the all-to-all layout unchanged.
 """
 
 from __future__ import annotations
@@ -19,7 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.fused import FusedLayerNorm
-from ..ops.moe import moe_combine, moe_dispatch, moe_fusable, moe_route_top1
+from ..ops.moe import (moe_combine, moe_dispatch, moe_fusable, moe_route_top1,
+                       moe_route_topk)
 
 
 class _AllToAll(torch.autograd.Function):
@@ -57,7 +65,8 @@ class Expert(nn.Module):
 
 class MoEMLP(nn.Module):
     """Distributed MoE MLP: ``num_local_experts`` experts per rank,
-    ``world_size * num_local_experts`` experts total, top-1 gate."""
+    ``world_size * num_local_experts`` experts total, top-1 gate; ``top_k=2``
+    and ``balance_loss`` as described in the module docstring."""
 
     def __init__(
         self,
@@ -69,9 +78,20 @@ class MoEMLP(nn.Module):
         rank: int = 0,
         capacity_factor: float = 1.25,
         fused_routing: bool = True,
+        top_k: int = 1,
+        normalize_gates: bool = True,
+        balance_loss: bool = False,
     ):
         super().__init__()
+        if top_k not in (1, 2):
+            raise ValueError("MoEMLP: top_k must be 1 or 2")
+        if world_size * num_local_experts < top_k:
+            raise ValueError("MoEMLP: need at least top_k experts")
         self.fused_routing = fused_routing
+        self.top_k = top_k
+        self.normalize_gates = normalize_gates
+        self.balance_loss = balance_loss
+        self.aux_loss = None  # balance loss of the last forward
         self.comm = comm
         self.world_size = world_size
         self.rank = rank
@@ -89,6 +109,8 @@ class MoEMLP(nn.Module):
         x = x.reshape(-1, self.d_model)
         T = x.shape[0]
         E = self.num_experts
+        if self.top_k != 1 or self.balance_loss:
+            return self._forward_topk(x).view(orig_shape)
         cap = max(1, math.ceil(T / E * self.capacity_factor))
 
         logits = self.gate(x)
@@ -156,6 +178,37 @@ class MoEMLP(nn.Module):
             self.comm, out.view(self.world_size, self.num_local * cap,
                                 self.d_model))
         return moe_combine(back.reshape(-1, self.d_model), routing)
+
+    def _forward_topk(self, x: torch.Tensor) -> torch.Tensor:
+        """Top-k gate with GShard capacity priority and the balance loss, on
+        ``moe_route_topk``: the HIP kernels where they apply and
+        ``fused_routing`` is set, the plain-torch ops otherwise. Exchange and
+        expert loop are those of ``forward``."""
+        T = x.shape[0]
+        k = self.top_k
+        cap = max(1, math.ceil(k * T / self.num_experts
+                               * self.capacity_factor))
+        logits = self.gate(x)
+        fused = self.fused_routing and moe_fusable(x, logits, cap, k)
+        routing = moe_route_topk(logits, k, cap, self.normalize_gates,
+                                 use_kernels=fused)
+        self.aux_loss = routing.aux_loss
+        dispatch = moe_dispatch(x, routing, use_kernels=fused)
+        dispatch = dispatch.view(self.world_size, self.num_local * cap,
+                                 self.d_model)
+        recv = _AllToAll.apply(self.comm, dispatch)
+        recv = recv.view(self.world_size, self.num_local, cap, self.d_model)
+        outs = []
+        for i, expert in enumerate(self.experts):
+            outs.append(expert(recv[:, i].reshape(-1, self.d_model)))
+        out = torch.stack(outs, dim=1)
+        out = out.view(self.world_size, cap, self.num_local, self.d_model)
+        out = out.permute(0, 2, 1, 3).contiguous()
+        back = _AllToAll.apply(
+            self.comm, out.view(self.world_size, self.num_local * cap,
+                                self.d_model))
+        return moe_combine(back.reshape(-1, self.d_model), routing,
+                           use_kernels=fused)
 
 
 class MoETransformerBlock(nn.Module):

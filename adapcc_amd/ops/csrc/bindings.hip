@@ -120,11 +120,26 @@ void moe_route(int dtype, const void* logits, float* gate_p, int* expert,
 void moe_route_bwd(int dtype, const void* logits, const float* gate_p,
                    const int* expert, const int* slot, const float* dgate,
                    void* dlogits, long ntok, long E, hipStream_t stream);
+void moe_route_topk(int dtype, const void* logits, int k, int normalize,
+                    float* gate, float* pmax, int* expert, int* slot,
+                    int* src, int* src_choice, int* load, float* aux,
+                    int* counts, int* offs, int* totals, float* psum,
+                    long ntok, long E, long cap, hipStream_t stream);
+void moe_route_topk_bwd(int dtype, const void* logits, int k, int normalize,
+                        const float* pmax, const float* gate,
+                        const int* expert, const int* slot,
+                        const float* dgate, const int* load,
+                        const float* daux, void* dlogits, long ntok, long E,
+                        hipStream_t stream);
 void moe_gather(int dtype, const void* in, long in_rows, const int* map,
-                const float* scale, int scale_by_src, void* out, long rows,
-                long d, hipStream_t stream);
+                const float* scale, int scale_by_src, const int* choice,
+                int nchoice, void* out, long rows, long d,
+                hipStream_t stream);
+void moe_gather2(int dtype, const void* in, long in_rows, const int* map,
+                 const float* scale, void* out, long rows, long d,
+                 hipStream_t stream);
 void moe_rowdot(int dtype, const void* a, const void* b, long b_rows,
-                const int* map, float* out, long rows, long d,
+                const int* map, float* out, long rows, long d, int a_shift,
                 hipStream_t stream);
 void tr_probe(float* out, int kb, int db, hipStream_t stream);
 void pack_probe(float* out, hipStream_t stream);
@@ -356,23 +371,69 @@ PYBIND11_MODULE(_core, m) {
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
-  // scale = 0: plain copy; scale_by_src picks scale[map[r]] over scale[r]
+  // Top-k routing, k in {1, 2}: counts/offs are int32 workspaces of
+  // k*ceil(T/256)*E elements, totals of E, psum fp32 of ceil(T/256)*E.
+  m.def("moe_route_topk",
+        [](int dtype, uintptr_t logits, int k, bool normalize, uintptr_t gate,
+           uintptr_t pmax, uintptr_t expert, uintptr_t slot, uintptr_t src,
+           uintptr_t src_choice, uintptr_t load, uintptr_t aux,
+           uintptr_t counts, uintptr_t offs, uintptr_t totals, uintptr_t psum,
+           long ntok, long E, long cap, uintptr_t stream) {
+          adapcc::moe_route_topk(
+              dtype, (const void*)logits, k, normalize ? 1 : 0, (float*)gate,
+              (float*)pmax, (int*)expert, (int*)slot, (int*)src,
+              (int*)src_choice, (int*)load, (float*)aux, (int*)counts,
+              (int*)offs, (int*)totals, (float*)psum, ntok, E, cap,
+              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // daux = 0: the balance loss received no gradient
+  m.def("moe_route_topk_bwd",
+        [](int dtype, uintptr_t logits, int k, bool normalize, uintptr_t pmax,
+           uintptr_t gate, uintptr_t expert, uintptr_t slot, uintptr_t dgate,
+           uintptr_t load, uintptr_t daux, uintptr_t dlogits, long ntok,
+           long E, uintptr_t stream) {
+          adapcc::moe_route_topk_bwd(
+              dtype, (const void*)logits, k, normalize ? 1 : 0,
+              (const float*)pmax, (const float*)gate, (const int*)expert,
+              (const int*)slot, (const float*)dgate, (const int*)load,
+              (const float*)daux, (void*)dlogits, ntok, E,
+              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // scale = 0: plain copy; scale_by_src picks scale[map[r]] over scale[r];
+  // choice != 0: scale is [in_rows, nchoice], taken at (map[r], choice[r])
   m.def("moe_gather",
         [](int dtype, uintptr_t in, long in_rows, uintptr_t map,
-           uintptr_t scale, bool scale_by_src, uintptr_t out, long rows,
-           long d, uintptr_t stream) {
+           uintptr_t scale, bool scale_by_src, uintptr_t choice, int nchoice,
+           uintptr_t out, long rows, long d, uintptr_t stream) {
           adapcc::moe_gather(dtype, (const void*)in, in_rows, (const int*)map,
                              (const float*)scale, scale_by_src ? 1 : 0,
-                             (void*)out, rows, d,
+                             (const int*)choice, nchoice, (void*)out, rows, d,
                              reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
+  // map and scale are [rows, 2]; scale = 0: plain sum
+  m.def("moe_gather2",
+        [](int dtype, uintptr_t in, long in_rows, uintptr_t map,
+           uintptr_t scale, uintptr_t out, long rows, long d,
+           uintptr_t stream) {
+          adapcc::moe_gather2(dtype, (const void*)in, in_rows,
+                              (const int*)map, (const float*)scale,
+                              (void*)out, rows, d,
+                              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // a has rows >> a_shift rows (a_shift 1: two map entries per row of a)
   m.def("moe_rowdot",
         [](int dtype, uintptr_t a, uintptr_t b, long b_rows, uintptr_t map,
-           uintptr_t out, long rows, long d, uintptr_t stream) {
+           uintptr_t out, long rows, long d, int a_shift, uintptr_t stream) {
           adapcc::moe_rowdot(dtype, (const void*)a, (const void*)b, b_rows,
-                             (const int*)map, (float*)out, rows, d,
+                             (const int*)map, (float*)out, rows, d, a_shift,
                              reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));

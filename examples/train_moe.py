@@ -6,6 +6,10 @@ hook).
 
     python -m torch.distributed.run --nproc-per-node 8 \
         --master-addr 127.0.0.1 examples/train_moe.py
+
+``--top-k 2`` routes every token to its two best experts; a non-zero
+``--aux-coef`` adds that multiple of the layer's load-balancing loss to the
+training loss (0.01 is the usual Switch/GShard value).
 """
 
 from __future__ import annotations
@@ -32,6 +36,9 @@ def main():
     p.add_argument("--d_model", type=int, default=1024)
     p.add_argument("--d_hidden", type=int, default=4096)
     p.add_argument("--local_experts", type=int, default=2)
+    p.add_argument("--top-k", type=int, default=1, choices=(1, 2))
+    p.add_argument("--aux-coef", type=float, default=0.0,
+                   help="weight of the load-balancing loss (0 = off)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -53,7 +60,7 @@ def main():
     model = MoETransformerBlock(
         d_model=args.d_model, n_head=8, d_hidden=args.d_hidden,
         num_local_experts=args.local_experts, comm=comm, world_size=world,
-        rank=rank,
+        rank=rank, top_k=args.top_k, balance_loss=args.aux_coef != 0.0,
     ).to(device)
     # expert weights are rank-local (expert parallel): re-init per rank
     torch.manual_seed(100 + rank)
@@ -73,6 +80,8 @@ def main():
         opt.zero_grad(set_to_none=True)
         y = model(x)
         loss = (y ** 2).mean()
+        if args.aux_coef != 0.0:
+            loss = loss + args.aux_coef * model.moe.aux_loss
         loss.backward()
         # dense (non-expert) grads sync across ranks; expert grads stay local
         if world > 1:
