@@ -55,9 +55,19 @@ class CausalSelfAttention(nn.Module):
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
         self.dropout = cfg.dropout
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor,
+                cu_seqlens: torch.Tensor = None) -> torch.Tensor:
         from ..ops import attention
 
+        p = self.dropout if self.training else 0.0
+        if cu_seqlens is not None:
+            # x is [1,total,C], documents back to back: attention stays
+            # inside each document, on the [total,3C] view
+            qkv = self.c_attn(x)
+            y = attention.flash_attention_qkv_varlen(
+                qkv.view(qkv.shape[1], qkv.shape[2]), self.n_head,
+                cu_seqlens, dropout_p=p)
+            return self.c_proj(y.view(1, y.shape[0], y.shape[1]))
         # packed [B,T,3C] in, [B,T,C] out: no split/transpose copies
         return self.c_proj(attention.flash_attention_qkv(
             self.c_attn(x), self.n_head,
@@ -85,23 +95,29 @@ class Block(nn.Module):
         self.ln_2 = FusedLayerNorm(cfg.n_embd)
         self.mlp = MLP(cfg)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x: torch.Tensor,
+                cu_seqlens: torch.Tensor = None) -> torch.Tensor:
+        if cu_seqlens is None:
+            x = x + self.attn(self.ln_1(x))
+        else:
+            x = x + self.attn(self.ln_1(x), cu_seqlens)
         x = x + self.mlp(self.ln_2(x))
         return x
 
     def forward_resid_dropout(self, x: torch.Tensor, y: torch.Tensor,
-                              next_ln: nn.LayerNorm, p: float, site: int):
+                              next_ln: nn.LayerNorm, p: float, site: int,
+                              cu_seqlens: torch.Tensor = None):
         """The block with residual dropout p. x: the residual stream, y =
         ln_1(x), already computed where x was. Each sublayer output goes
         through one fused dropout + add + LayerNorm: the attention's with
         ln_2, the MLP's with next_ln (the next block's ln_1, or ln_f).
         Returns the new stream and next_ln of it; uses mask sites site and
-        site + 1."""
+        site + 1. cu_seqlens: as in forward."""
         from ..ops.fused import fused_dropout_add_layer_norm
 
+        a = self.attn(y) if cu_seqlens is None else self.attn(y, cu_seqlens)
         x, y = fused_dropout_add_layer_norm(
-            self.attn(y), x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps,
+            a, x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps,
             dropout_p=p, site=site)
         return fused_dropout_add_layer_norm(
             self.mlp(y), x, next_ln.weight, next_ln.bias, next_ln.eps,
@@ -140,9 +156,37 @@ class GPT2(nn.Module):
             n -= self.wpe.weight.numel()
         return n
 
-    def forward(self, idx: torch.Tensor, targets: torch.Tensor = None):
+    def _packed_positions(self, cu_seqlens: torch.Tensor,
+                          total: int) -> torch.Tensor:
+        """Position ids that restart at every document start, from
+        cu_seqlens on the device (no host sync). Clamped into the position
+        table, so a malformed cu_seqlens cannot index outside it."""
+        rows = torch.arange(total, dtype=torch.int32,
+                            device=cu_seqlens.device)
+        ends = cu_seqlens[1:].contiguous()
+        doc = torch.bucketize(rows, ends, right=True)
+        doc = doc.clamp_(max=ends.numel() - 1)
+        pos = rows - cu_seqlens[:-1][doc]
+        return pos.clamp_(0, self.cfg.n_positions - 1).long()
+
+    def forward(self, idx: torch.Tensor, targets: torch.Tensor = None,
+                cu_seqlens: torch.Tensor = None):
+        """cu_seqlens (int32 [n_docs + 1] on idx's device, non-decreasing
+        from 0 to total): idx is [1,total] and holds documents back to back,
+        each at most n_positions long; total may exceed n_positions.
+        Position ids restart at each document and attention stays inside
+        it. The caller masks the targets that cross a document boundary
+        with the loss' ignore_index (-100)."""
         B, T = idx.shape
-        pos = torch.arange(T, device=idx.device)
+        if cu_seqlens is None:
+            pos = torch.arange(T, device=idx.device)
+            kw = {}
+        else:
+            if B != 1:
+                raise ValueError("GPT2.forward: with cu_seqlens idx must be "
+                                 f"[1, total], got {tuple(idx.shape)}")
+            pos = self._packed_positions(cu_seqlens, T)
+            kw = {"cu_seqlens": cu_seqlens}
         x = self.drop(self.wte(idx) + self.wpe(pos))
         if self.training and self.cfg.resid_dropout > 0.0:
             # every LayerNorm but the first runs fused with the add (and
@@ -151,11 +195,11 @@ class GPT2(nn.Module):
             y = self.h[0].ln_1(x)
             for i, block in enumerate(self.h):
                 x, y = block.forward_resid_dropout(
-                    x, y, lns[i], self.cfg.resid_dropout, site=2 * i)
+                    x, y, lns[i], self.cfg.resid_dropout, site=2 * i, **kw)
             x = y
         else:
             for block in self.h:
-                x = block(x)
+                x = block(x, **kw)
             x = self.ln_f(x)
         logits = self.lm_head(x)
         loss = None

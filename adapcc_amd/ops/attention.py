@@ -19,6 +19,20 @@ sees a fresh mask on every replay), or passed as ``dropout_seed``. It is
 this project's own stream, not the Philox one of torch SDPA.
 ``dropout_keep_mask_reference`` is the same function in torch integer ops,
 ``fa_dropout_mask`` the kernels' own answer.
+
+A third mode takes sequences of any lengths packed back to back:
+``flash_attention_varlen`` on [total,H,D] tensors and
+``flash_attention_qkv_varlen`` on the packed [total,3C] projection, both
+with ``cu_seqlens`` (int32 [n_seqs + 1] row offsets on the device), causal
+or not, with the same dropout. Attention is block-diagonal: a row sees only
+its own sequence. No padding, no length condition and no host sync: a small
+plan kernel turns ``cu_seqlens`` into the map from workgroup to (sequence,
+tile) on the device (``varlen_tile_map_reference`` is its definition), so
+the call can sit in a captured graph whose ``cu_seqlens`` is refilled
+between replays. The dropout mask of sequence i, head h is plane i * H + h
+of the same function, q and k counted from the sequence start. Off the
+kernel path the same function is composed from torch SDPA under a
+block-diagonal mask.
 """
 
 from __future__ import annotations
@@ -32,7 +46,9 @@ from .fused import _core
 
 __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
            "fa_qkv_supported", "fa_dropout_mask",
-           "dropout_keep_mask_reference"]
+           "dropout_keep_mask_reference", "flash_attention_varlen",
+           "flash_attention_qkv_varlen", "fa_varlen_supported",
+           "fa_qkv_varlen_supported", "varlen_tile_map_reference"]
 
 
 def _strides3(t: torch.Tensor):
@@ -331,3 +347,322 @@ def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
                                      seed)
     return _attention_qkv_composed(qkv, n_head, dropout_p, causal,
                                    dropout_seed)
+
+
+# ---------------------------------------------------------------------------
+# Variable-length (packed sequences) attention
+# ---------------------------------------------------------------------------
+_QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
+
+
+def _check_cu_seqlens(name: str, cu_seqlens, device: torch.device) -> None:
+    """Shape, dtype and device of cu_seqlens; its contents are never read
+    on the host."""
+    if not isinstance(cu_seqlens, torch.Tensor):
+        raise ValueError(f"{name}: cu_seqlens must be a tensor")
+    if cu_seqlens.dtype != torch.int32:
+        raise ValueError(f"{name}: cu_seqlens must be int32, got "
+                         f"{cu_seqlens.dtype}")
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2:
+        raise ValueError(f"{name}: cu_seqlens must be 1-D with n_seqs + 1 "
+                         f">= 2 elements, got shape "
+                         f"{tuple(cu_seqlens.shape)}")
+    if cu_seqlens.device != device:
+        raise ValueError(f"{name}: cu_seqlens is on {cu_seqlens.device}, "
+                         f"the inputs on {device}")
+
+
+def _cu_ok(cu_seqlens, device: torch.device) -> bool:
+    try:
+        _check_cu_seqlens("", cu_seqlens, device)
+    except ValueError:
+        return False
+    return cu_seqlens.is_contiguous() and cu_seqlens.data_ptr() % 4 == 0
+
+
+def _rows4(t: torch.Tensor) -> torch.Tensor:
+    """[total,H,D] -> its [1,H,total,D] view, the kernels' tensor form."""
+    return t.unsqueeze(0).transpose(1, 2)
+
+
+def _varlen_kernel_ok(t: torch.Tensor, D: int, total: int,
+                      dropout_p: float) -> bool:
+    """_kernel_ok without a length condition: any total >= 1."""
+    return _kernel_ok(t, D, total, False, dropout_p)
+
+
+def fa_varlen_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                        cu_seqlens: torch.Tensor, causal: bool,
+                        dropout_p: float) -> bool:
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+        return False
+    if not _cu_ok(cu_seqlens, q.device):
+        return False
+    if not all(_row_ok(_rows4(t)) for t in (q, k, v)):
+        return False
+    return _varlen_kernel_ok(q, q.shape[2], q.shape[0], dropout_p)
+
+
+def fa_qkv_varlen_supported(qkv: torch.Tensor, n_head: int,
+                            cu_seqlens: torch.Tensor, dropout_p: float,
+                            causal: bool = True) -> bool:
+    if qkv.dim() != 2 or qkv.shape[1] % (3 * n_head):
+        return False
+    if not _cu_ok(cu_seqlens, qkv.device):
+        return False
+    if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
+        return False
+    return _varlen_kernel_ok(qkv, qkv.shape[1] // (3 * n_head),
+                             qkv.shape[0], dropout_p)
+
+
+def varlen_tile_map_reference(cu_seqlens, total: int) -> torch.Tensor:
+    """The plan of the variable-length kernels in plain Python: the int32
+    [total // 128 + n_seqs, 4] map whose rows are (seq, tile, start, len),
+    one per 128-row tile in sequence order, then -1 rows. This is the
+    definition ``_core.fa_varlen_plan`` is held to.
+
+    Sequence i is rows [e_i, e_i+1) with e_i = clamp(max(cu[0..i]), 0,
+    total). On a well-formed vector that is cu_seqlens itself; on any other
+    the sequences are still disjoint and inside [0, total), so their tiles
+    fit the map and no kernel that follows it leaves the buffers. A sequence
+    that comes out empty has no tile."""
+    cu = [int(x) for x in torch.as_tensor(cu_seqlens).tolist()]
+    total = int(total)
+    n_seqs = len(cu) - 1
+    if n_seqs < 1 or total < 1:
+        raise ValueError("varlen_tile_map_reference: need n_seqs >= 1 and "
+                         "total >= 1")
+
+    def clamp(x):
+        return min(max(x, 0), total)
+
+    rows = []
+    m = cu[0]
+    for i in range(n_seqs):
+        e = clamp(m)
+        m = max(m, cu[i + 1])
+        length = clamp(m) - e
+        rows += [(i, j, e, length) for j in range(-(-length // _QT))]
+    max_tiles = total // _QT + n_seqs
+    assert len(rows) <= max_tiles
+    rows += [(-1, -1, -1, -1)] * (max_tiles - len(rows))
+    return torch.tensor(rows, dtype=torch.int32).view(max_tiles, 4)
+
+
+def _varlen_plan(cu_seqlens: torch.Tensor, total: int) -> torch.Tensor:
+    """Runs the plan kernel on the current stream; no host sync."""
+    n_seqs = cu_seqlens.numel() - 1
+    tmap = torch.empty((total // _QT + n_seqs, 4), dtype=torch.int32,
+                       device=cu_seqlens.device)
+    stream = torch.cuda.current_stream(cu_seqlens.device).cuda_stream
+    _core().fa_varlen_plan(cu_seqlens.data_ptr(), n_seqs, total,
+                           tmap.data_ptr(), stream)
+    return tmap
+
+
+def _launch_varlen_fwd(q, k, v, o, lse, tmap, n_seqs, scale, causal=True,
+                       dropout_p=0.0, seed=None):
+    """q, k, v, o: [1,H,total,D] views; lse: [H,total] fp32."""
+    _, H, total, _ = q.shape
+    strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _core().fa_varlen_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                          o.data_ptr(), lse.data_ptr(), tmap.data_ptr(),
+                          total, n_seqs, H, strides, scale, stream, causal,
+                          dropout_p,
+                          seed.data_ptr() if dropout_p > 0.0 else 0)
+
+
+def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
+                       scale, causal=True, delta=None, dropout_p=0.0,
+                       seed=None):
+    """As _launch_bwd on [1,H,total,D] views; the delta workspace is
+    contiguous [H,total] fp32."""
+    _, H, total, _ = q.shape
+    do = dout if _row_ok(dout) else dout.contiguous()
+    if delta is None:
+        delta = torch.empty((H, total), dtype=torch.float32,
+                            device=q.device)
+    strides = (_strides3(q) + _strides3(k) + _strides3(v) + _strides3(o) +
+               _strides3(do) + _strides3(dq) + _strides3(dk) +
+               _strides3(dv))
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _core().fa_varlen_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                          o.data_ptr(), do.data_ptr(), lse.data_ptr(),
+                          delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                          dv.data_ptr(), tmap.data_ptr(), total, n_seqs, H,
+                          strides, scale, stream, causal, dropout_p,
+                          seed.data_ptr() if dropout_p > 0.0 else 0)
+
+
+def _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale, causal,
+                           dropout_p=0.0, seed=None):
+    """Forward only: (o [total,H,D], lse [H,total] fp32, tile map)."""
+    total, H, D = q.shape
+    tmap = _varlen_plan(cu_seqlens, total)
+    o = torch.empty((total, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((H, total), dtype=torch.float32, device=q.device)
+    _launch_varlen_fwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o), lse, tmap,
+                       cu_seqlens.numel() - 1, scale, causal=causal,
+                       dropout_p=dropout_p, seed=seed)
+    return o, lse, tmap
+
+
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    """[total,H,D] q, k, v that hold sequences back to back, cu_seqlens
+    their int32 row offsets. seed as in _FlashAttnFn."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, scale, causal, dropout_p=0.0,
+                seed=None):
+        ctx.scale, ctx.causal, ctx.dropout_p = scale, causal, dropout_p
+        o, lse, tmap = _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale,
+                                              causal, **_drop_kw(ctx, seed))
+        if dropout_p > 0.0:
+            ctx.save_for_backward(q, k, v, o, lse, tmap, cu_seqlens, seed)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse, tmap, cu_seqlens)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        dk = torch.empty_like(dq)
+        dv = torch.empty_like(dq)
+        _launch_varlen_bwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o),
+                           _rows4(dout), lse, _rows4(dq), _rows4(dk),
+                           _rows4(dv), tmap, cu_seqlens.numel() - 1,
+                           ctx.scale, causal=ctx.causal,
+                           **_drop_kw(ctx, seed[0] if seed else None))
+        return dq, dk, dv, None, None, None, None, None
+
+
+def _heads2(t: torch.Tensor, n_head: int) -> torch.Tensor:
+    """[total,C] (any row stride) -> its [1,H,total,C/H] view."""
+    return _heads(t.unsqueeze(0), n_head)
+
+
+class _FlashAttnQkvVarlenFn(torch.autograd.Function):
+    """_FlashAttnQkvFn for packed sequences: q, k, v are strided views of
+    qkv [total,3C], O is written as [total,C], and the backward writes dq,
+    dk, dv into the three thirds of one [total,3C] gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_head, cu_seqlens, scale, causal, dropout_p=0.0,
+                seed=None):
+        total, C3 = qkv.shape
+        C = C3 // 3
+        q, k, v = (_heads2(t, n_head) for t in qkv.split(C, dim=1))
+        tmap = _varlen_plan(cu_seqlens, total)
+        y = torch.empty((total, C), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((n_head, total), dtype=torch.float32,
+                          device=qkv.device)
+        ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
+        ctx.dropout_p = dropout_p
+        _launch_varlen_fwd(q, k, v, _heads2(y, n_head), lse, tmap,
+                           cu_seqlens.numel() - 1, scale, causal=causal,
+                           **_drop_kw(ctx, seed))
+        if dropout_p > 0.0:
+            ctx.save_for_backward(qkv, y, lse, tmap, cu_seqlens, seed)
+        else:
+            ctx.save_for_backward(qkv, y, lse, tmap, cu_seqlens)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        qkv, y, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
+        H = ctx.n_head
+        C = y.shape[1]
+        q, k, v = (_heads2(t, H) for t in qkv.split(C, dim=1))
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = (_heads2(t, H) for t in dqkv.split(C, dim=1))
+        _launch_varlen_bwd(q, k, v, _heads2(y, H), _heads2(dy, H), lse, dq,
+                           dk, dv, tmap, cu_seqlens.numel() - 1, ctx.scale,
+                           causal=ctx.causal,
+                           **_drop_kw(ctx, seed[0] if seed else None))
+        return dqkv, None, None, None, None, None, None
+
+
+def _varlen_mask(cu_seqlens: torch.Tensor, total: int,
+                 causal: bool) -> torch.Tensor:
+    """[total,total] bool, True where q row (dim 0) may see k row (dim 1):
+    same sequence, and k <= q when causal. Built on cu_seqlens' device with
+    no host sync."""
+    rows = torch.arange(total, dtype=torch.int32, device=cu_seqlens.device)
+    # sequence id of a row = number of sequence ends <= row
+    sid = torch.bucketize(rows, cu_seqlens[1:].contiguous(), right=True)
+    mask = sid.view(-1, 1) == sid.view(1, -1)
+    if causal:
+        mask = mask & (rows.view(1, -1) <= rows.view(-1, 1))
+    return mask
+
+
+def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                           cu_seqlens: torch.Tensor, causal: bool = True,
+                           dropout_p: float = 0.0, scale: float = None,
+                           dropout_seed: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
+    """Self-attention over sequences packed back to back. q, k, v:
+    [total,H,D] (any row and head strides); cu_seqlens: int32 [n_seqs + 1]
+    on the same device, sequence i owning rows cu_seqlens[i] ..
+    cu_seqlens[i+1]-1. A row attends only inside its own sequence (and to
+    keys at or before itself when causal). Returns [total,H,D].
+
+    Contract for cu_seqlens, which is never read on the host and so not
+    checked: non-decreasing, first entry 0, last entry total. Zero-length
+    sequences are fine anywhere. A vector that breaks the contract gives
+    unspecified values but no access outside the tensors.
+
+    bf16 on the GPU with D = 64 runs the CDNA4 kernels (any lengths, no
+    padding, no host sync; dropout mask plane seq * H + h with q and k
+    counted from the sequence start); anything else runs torch SDPA under
+    the block-diagonal mask, with torch's dropout."""
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+        raise ValueError("flash_attention_varlen: q, k, v must be "
+                         "[total,H,D] of one shape, got "
+                         f"{tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    _check_cu_seqlens("flash_attention_varlen", cu_seqlens, q.device)
+    if fa_varlen_supported(q, k, v, cu_seqlens, causal, dropout_p):
+        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        seed = (_seed_tensor(dropout_seed, q.device) if dropout_p > 0.0
+                else None)
+        return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens, s, causal,
+                                        dropout_p, seed)
+    mask = _varlen_mask(cu_seqlens, q.shape[0], causal)
+    y = torch.nn.functional.scaled_dot_product_attention(
+        _rows4(q), _rows4(k), _rows4(v), attn_mask=mask,
+        dropout_p=dropout_p, scale=scale)
+    return y.squeeze(0).transpose(0, 1)
+
+
+def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
+                               cu_seqlens: torch.Tensor,
+                               dropout_p: float = 0.0, causal: bool = True,
+                               dropout_seed: Optional[torch.Tensor] = None
+                               ) -> torch.Tensor:
+    """``flash_attention_varlen`` on the packed projection qkv [total,3C]
+    (q, k, v thirds, heads contiguous within each); returns [total,C]. The
+    qualifying case (bf16, head_dim 64, contiguous, dropout_p < 1) runs the
+    kernels directly on the packed layout with no copies; anything else
+    composes ``flash_attention_varlen`` from views. cu_seqlens: see there."""
+    if qkv.dim() != 2 or qkv.shape[1] % (3 * n_head):
+        raise ValueError("flash_attention_qkv_varlen: qkv must be "
+                         f"[total, 3 * n_head * D], got {tuple(qkv.shape)}")
+    _check_cu_seqlens("flash_attention_qkv_varlen", cu_seqlens, qkv.device)
+    total, C3 = qkv.shape
+    C = C3 // 3
+    if fa_qkv_varlen_supported(qkv, n_head, cu_seqlens, dropout_p, causal):
+        scale = 1.0 / math.sqrt(C // n_head)
+        seed = (_seed_tensor(dropout_seed, qkv.device) if dropout_p > 0.0
+                else None)
+        return _FlashAttnQkvVarlenFn.apply(qkv, n_head, cu_seqlens, scale,
+                                           causal, dropout_p, seed)
+    q, k, v = (t.view(total, n_head, C // n_head)
+               for t in qkv.split(C, dim=1))
+    y = flash_attention_varlen(q, k, v, cu_seqlens, causal=causal,
+                               dropout_p=dropout_p,
+                               dropout_seed=dropout_seed)
+    return y.contiguous().view(total, C)

@@ -1,6 +1,8 @@
-// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim=64, in two
-// modes: causal with S % 128 == 0 (GPT-2), and non-causal self-attention
-// over any S >= 1 (ViT: S = 197).
+// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim=64, in three
+// modes: causal with S % 128 == 0 (GPT-2), non-causal self-attention over
+// any S >= 1 (ViT: S = 197), and variable-length, causal or not, over
+// sequences of any lengths packed back to back in [total, H, 64] tensors
+// with cu_seqlens (GPT-2 on documents).
 //
 // Replaces the stock SDPA path for the GPT-2 flagship workload, where the
 // aotriton kernels ran at ~2% of the MFMA roof (rocprof round-1 evidence:
@@ -19,11 +21,11 @@
 // backward splits FA2-style into a dq kernel (q-tile outer) and a dkv
 // kernel (kv-tile outer), both recomputing P from the saved logsumexp.
 //
-// The three kernels are templates on <kCausal, kRagged, kDrop>.
-// <true,false,false> is the GPT-2 case. kDrop adds attention dropout on P
-// (mask function in attn_drop.h): the forward zeroes dropped P after the row
-// sum, so the normaliser and lse are those of the undropped scores, and
-// folds 1/(1-p) into the epilogue's 1/rowsum; delta = rowsum(dO*O) needs no
+// The three kernels are templates on <kCausal, kRagged, kDrop, kVarlen>.
+// <true,false,false,false> is the GPT-2 case. kDrop adds attention dropout
+// on P (mask function in attn_drop.h): the forward zeroes dropped P after
+// the row sum, so the normaliser and lse are those of the undropped scores,
+// and folds 1/(1-p) into the epilogue's 1/rowsum; delta = rowsum(dO*O) needs no
 // change since O carries the dropout; the backward regenerates the mask and
 // forms dS = P * (keep * dP/(1-p) - delta) * scale and
 // dV = (P*keep)^T dO / (1-p), the last factor on the fp32 accumulator. The
@@ -37,6 +39,18 @@
 // (P forced to 0 in the backward), predicates every store on row < S, and
 // skips the MFMA/softmax work of 32-row half-tiles and of waves that are
 // all padding (those waves still stage and take every barrier).
+// kVarlen (always with kRagged) is that ragged code run per sequence: a
+// plan kernel turns cu_seqlens into a (seq, tile, start, len) map on the
+// device, the launch has total/128 + n_seqs workgroups in x and the heads
+// in y, and a workgroup takes its tile, its length S = len and its first
+// row from the map (an unused entry leaves before the first barrier); every
+// row index is local to the sequence, lse and delta are [H, total], the
+// dropout plane is seq*H + h. Its causal form is the one place where
+// kCausal and kRagged meet: the tile loop stops at the diagonal or at
+// ceil(S/64), whichever comes first, a row sees keys <= min(q, S-1), and
+// in the dkv kernel q rows >= S get P = dS = 0. A valid row then computes
+// bit for bit what the fixed-length causal kernel computes for it on the
+// sequence zero-padded to a multiple of 128.
 //
 // Reference parity note: the reference (JoeyYoung/adapcc) has no attention
 // kernels (models used stock torch); this op exists to meet BASELINE.json's
@@ -91,7 +105,43 @@ struct FaParams {
   const long* seed;    // device memory: a graph replay sees a fresh value
   unsigned drop_thr;   // keep iff word >= drop_thr
   float drop_rp;       // 1/(1-p)
+  // variable-length mode, kVarlen instantiations only (both directions)
+  const int4* tmap;    // [gridDim.x] (seq, tile, start, len), seq < 0: unused
+  int total;           // packed rows; lse and delta are [H, total]
 };
+
+// Variable-length mode: q, k, v, ... are [total, H, 64] views that hold the
+// sequences back to back, and workgroup x of the launch owns the 128-row
+// tile `tile` of sequence `seq`, rows start .. start+len-1 of the packed
+// buffer, as the plan kernel (below) wrote it into tmap[x]. The kernels take
+// start and len from the map alone, never from cu_seqlens, so the plan's
+// clamping bounds every address. Inside the sequence the code is the ragged
+// one with S = len and all row indices local; the mask plane is seq*H + h.
+struct VarlenTile {
+  int seq, tile, start, len;
+};
+
+__device__ __forceinline__ VarlenTile varlen_tile(const FaParams& p) {
+  const int4 e = p.tmap[blockIdx.x];
+  return {e.x, e.y, e.z, e.w};
+}
+
+// Base of a kernel's rows in x: the (b, h) plane, or in the variable-length
+// mode head h from packed row row0 on.
+template <bool kVarlen, typename T>
+__device__ __forceinline__ T* seq_plane(T* x, const TStride& s, int b, int h,
+                                        long row0) {
+  if constexpr (kVarlen)
+    return x + (long)h * s.sh + row0 * s.ss;
+  else
+    return plane(x, s, b, h);
+}
+
+// An entry the plan left unused (or, should the map ever be stale, a tile
+// past its sequence): the workgroup leaves before its first barrier.
+__device__ __forceinline__ bool varlen_idle(const VarlenTile& t) {
+  return t.seq < 0 || (long)t.tile * kQT >= t.len;
+}
 
 // Row index used for a load: in the ragged mode rows >= S do not exist, so
 // they read row S-1 instead (real data, hence finite).
@@ -106,6 +156,24 @@ __device__ __forceinline__ long ld_row(long row, int S) {
 template <bool kRagged>
 __device__ __forceinline__ int ld_row32(int row, int S) {
   return kRagged ? min(row, S - 1) : row;
+}
+
+// 64-row KV tiles that q tile qt walks (forward, dq): up to the diagonal
+// when causal, to the last key when not; causal and ragged (the
+// variable-length mode) stops at whichever comes first.
+template <bool kCausal, bool kRagged>
+__device__ __forceinline__ int tile_count(int qt, int S) {
+  if (kCausal && kRagged) return min((qt + 1) * (kQT / 64), (S + 63) / 64);
+  return kCausal ? (qt + 1) * (kQT / 64) : (S + 63) / 64;
+}
+
+// Is key kglob hidden from q row qrow? qlim = min(qrow, S-1), used by the
+// causal ragged form alone.
+template <bool kCausal, bool kRagged>
+__device__ __forceinline__ bool key_masked(int kglob, int qrow, int qlim,
+                                           int S) {
+  if (kCausal && kRagged) return kglob > qlim;
+  return kCausal ? kglob > qrow : kglob >= S;
 }
 
 // ---------------------------------------------------------------------------
@@ -211,9 +279,10 @@ __device__ __forceinline__ float ds_elem(float pe, float dp, float delta,
 // Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
 // qt*128 + w*32 .. +31.
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged, bool kDrop>
+template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
 __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
-  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
+  static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
+                "fixed-length causal needs S % 128 == 0; varlen is ragged");
   // 64-row KV tiles, double-buffered: K images, then V images (then the
   // tiles' dropout k parts).
   __shared__ __attribute__((aligned(16))) char
@@ -226,19 +295,38 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
-  const int qt = blockIdx.x;
-  const int bh = blockIdx.y;
-  const int b = bh / p.H, h = bh % p.H;
+  // tile, mask plane, (b, h) of the tensor plane, length, and (varlen) the
+  // sequence's first packed row
+  int qt = blockIdx.x, bh = blockIdx.y, b, h, S = p.S;
+  long row0 = 0;
+  if constexpr (kVarlen) {
+    const VarlenTile vt = varlen_tile(p);
+    if (varlen_idle(vt)) return;
+    qt = vt.tile;
+    b = 0;
+    h = blockIdx.y;
+    bh = vt.seq * p.H + h;
+    S = vt.len;
+    row0 = vt.start;
+  } else {
+    b = bh / p.H;
+    h = bh % p.H;
+  }
 
-  const __bf16* qg = plane(p.q, p.qs, b, h);
-  const __bf16* kg = plane(p.k, p.ks, b, h);
-  const __bf16* vg = plane(p.v, p.vs, b, h);
-  __bf16* og = plane(p.o, p.os, b, h);
-  float* lseg = p.lse + (long)bh * p.S;
+  const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  __bf16* og = seq_plane<kVarlen>(p.o, p.os, b, h, row0);
+  float* lseg =
+      p.lse + (kVarlen ? (long)h * p.total + row0 : (long)bh * S);
 
   const int qb = qt * kQT + wave * 32;      // this wave's first q row
   const int qrow = qb + (lane & 31);        // this lane's q row
-  const long qld = ld_row<kRagged>((long)qrow, p.S);
+  const long qld = ld_row<kRagged>((long)qrow, S);
+  // causal and ragged: a row sees keys <= min(qrow, S-1). Rows >= S of the
+  // wave that holds row S-1 thereby repeat that row, loads and mask alike,
+  // so they never decide the wave-wide rescale below differently from it.
+  [[maybe_unused]] const int qlim = min(qrow, S - 1);
 
   // Q^T B-fragments, direct from global: lane l holds
   // Q[qrow][chunk*16 + 8*hi + e].
@@ -261,7 +349,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   const int srow = threadIdx.x >> 3;        // staging: this thread's row
   const int scol = (threadIdx.x & 7) * 8;   // and column (bf16)
   // 64-row tiles: up to the diagonal (causal) or all of them
-  const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
+  const int n64 = tile_count<kCausal, kRagged>(qt, S);
 
   // dropout: this lane's q part; seed_hi feeds the tiles' k parts
   [[maybe_unused]] unsigned dqa = 0, seed_hi = 0;
@@ -273,8 +361,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   // prologue: stage tile 0
   {
-    const long r0 = ld_row<kRagged>((long)srow, p.S);
-    const long r1 = ld_row<kRagged>((long)(srow + 32), p.S);
+    const long r0 = ld_row<kRagged>((long)srow, S);
+    const long r1 = ld_row<kRagged>((long)(srow + 32), S);
     st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
     st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
     if constexpr (kDrop)
@@ -290,8 +378,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
     const bool pref = t + 1 < n64;
     if (pref) {
       const long kb = (long)(t + 1) * 64 + srow;
-      const long kb0 = ld_row<kRagged>(kb, p.S);
-      const long kb1 = ld_row<kRagged>(kb + 32, p.S);
+      const long kb0 = ld_row<kRagged>(kb, S);
+      const long kb1 = ld_row<kRagged>(kb + 32, S);
       nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
       nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
       if constexpr (kDrop)
@@ -305,9 +393,10 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
       const int kbase = t * 64 + half * 32;
       if (kCausal) {
         if (kbase > qb + 31) break;  // wave-uniform causal cut
-      } else if (kRagged) {
+      }
+      if (kRagged) {
         // wave-uniform: a half-tile or a wave that is all padding
-        if (kbase >= p.S || qb >= p.S) break;
+        if (kbase >= S || qb >= S) break;
       }
       const char* ki = img(kimg, cur) + half * kHalfImg;
       const char* vi = img(vimg, cur) + half * kHalfImg;
@@ -322,13 +411,15 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
       float pv[16];
       float tmax = kNegBig;
-      if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
+      if ((kCausal && kbase + 31 > qb) || (kRagged && kbase + 31 >= S)) {
         // diagonal tile for this wave: apply the causal mask; ragged: the
         // tile that holds key S-1, mask the keys past it
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
-          pv[r] = (kCausal ? kglob > qrow : kglob >= p.S) ? kNegBig : s[r];
+          pv[r] = key_masked<kCausal, kRagged>(kglob, qrow, qlim, S)
+                      ? kNegBig
+                      : s[r];
           tmax = fmaxf(tmax, pv[r]);
         }
       } else {
@@ -396,7 +487,7 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   const float stot = ssum + __shfl_xor(ssum, 32, 64);
   float inv = 1.f / stot;
   if constexpr (kDrop) inv = p.drop_rp / stot;
-  if (kRagged && qrow >= p.S) return;  // stores only; no barrier follows
+  if (kRagged && qrow >= S) return;  // stores only; no barrier follows
   if ((lane >> 5) == 0)
     lseg[qrow] = p.scale * m + __builtin_amdgcn_logf(stot) * kLn2;
 
@@ -448,9 +539,10 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
   return (pr[0] + pr[1]) + (pr[2] + pr[3]);
 }
 
-template <bool kCausal, bool kRagged, bool kDrop>
+template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
 __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
-  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
+  static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
+                "fixed-length causal needs S % 128 == 0; varlen is ragged");
   // 64-row KV tiles, double-buffered: K images, then V images (then the
   // tiles' dropout k parts).
   __shared__ __attribute__((aligned(16))) char
@@ -463,20 +555,35 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
-  const int qt = blockIdx.x;
-  const int bh = blockIdx.y;
-  const int b = bh / p.H, h = bh % p.H;
+  int qt = blockIdx.x, bh = blockIdx.y, b, h, S = p.S;  // as in the forward
+  long row0 = 0;
+  if constexpr (kVarlen) {
+    const VarlenTile vt = varlen_tile(p);
+    if (varlen_idle(vt)) return;
+    qt = vt.tile;
+    b = 0;
+    h = blockIdx.y;
+    bh = vt.seq * p.H + h;
+    S = vt.len;
+    row0 = vt.start;
+  } else {
+    b = bh / p.H;
+    h = bh % p.H;
+  }
 
-  const __bf16* qg = plane(p.q, p.qs, b, h);
-  const __bf16* kg = plane(p.k, p.ks, b, h);
-  const __bf16* vg = plane(p.v, p.vs, b, h);
-  const __bf16* dog = plane(p.dout, p.dos_, b, h);
-  const __bf16* og = plane(p.o, p.os, b, h);
-  __bf16* dqg = plane(p.dq, p.dqs, b, h);
+  const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  const __bf16* dog = seq_plane<kVarlen>(p.dout, p.dos_, b, h, row0);
+  const __bf16* og = seq_plane<kVarlen>(p.o, p.os, b, h, row0);
+  __bf16* dqg = seq_plane<kVarlen>(p.dq, p.dqs, b, h, row0);
+  // first element of this plane's (varlen: this sequence's) lse and delta
+  const long lrow0 = kVarlen ? (long)h * p.total + row0 : (long)bh * S;
 
   const int qb = qt * kQT + wave * 32;
   const int qrow = qb + (lane & 31);
-  const long qld = ld_row32<kRagged>(qrow, p.S);
+  const long qld = ld_row32<kRagged>(qrow, S);
+  [[maybe_unused]] const int qlim = min(qrow, S - 1);  // see the forward
 
   // this lane holds 32 of its q row's 64 dO (and O) elements as four runs
   // of 8 (columns c*16 + hi*8 ..); lane^32 holds the runs in between. n16[c]
@@ -497,17 +604,17 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   for (int c = 0; c < 4; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(
         qg + qld * p.qs.ss + c * 16 + hi * 8);
-  const float lse2 = p.lse[(long)bh * p.S + qld] * kLog2e;
+  const float lse2 = p.lse[lrow0 + qld] * kLog2e;
   const float dvq = (n16[0] + n16[1]) + (n16[2] + n16[3]);
-  if (hi == 0 && (!kRagged || qrow < p.S))
-    p.delta[(long)bh * p.S + qrow] = dvq;
+  if (hi == 0 && (!kRagged || qrow < S))
+    p.delta[lrow0 + qrow] = dvq;
   const float c1 = p.scale * kLog2e;
 
   f32x16 dacc0 = {}, dacc1 = {};
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
-  const int n64 = kCausal ? (qt + 1) * (kQT / 64) : (p.S + 63) / 64;
+  const int n64 = tile_count<kCausal, kRagged>(qt, S);
 
   // dropout: this lane's q part; seed_hi feeds the tiles' k parts
   [[maybe_unused]] unsigned dqa = 0, seed_hi = 0;
@@ -517,8 +624,8 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
     seed_hi = (unsigned)(sd >> 32);
   }
   {
-    const long r0 = ld_row32<kRagged>(srow, p.S);
-    const long r1 = ld_row32<kRagged>(srow + 32, p.S);
+    const long r0 = ld_row32<kRagged>(srow, S);
+    const long r1 = ld_row32<kRagged>(srow + 32, S);
     st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
     st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
     if constexpr (kDrop)
@@ -532,8 +639,8 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
     RowPair nk, nv;
     const bool pref = t + 1 < n64;
     if (pref) {
-      const long kb0 = ld_row32<kRagged>((t + 1) * 64 + srow, p.S);
-      const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, p.S);
+      const long kb0 = ld_row32<kRagged>((t + 1) * 64 + srow, S);
+      const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, S);
       nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
       nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
       if constexpr (kDrop)
@@ -547,8 +654,9 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
       const int kbase = t * 64 + half * 32;
       if (kCausal) {
         if (kbase > qb + 31) break;
-      } else if (kRagged) {
-        if (kbase >= p.S || qb >= p.S) break;  // all padding
+      }
+      if (kRagged) {
+        if (kbase >= S || qb >= S) break;  // all padding
       }
       const char* ki = img(kimg, cur) + half * kHalfImg;
       const char* vi = img(vimg, cur) + half * kHalfImg;
@@ -579,18 +687,21 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
       if (kDrop) {
         // one loop: beside the mask word the compare is cheap, and the
         // second copy of the loop costs registers (scratch at 3 waves/SIMD)
-        const int lim = kCausal ? qrow : kRagged ? p.S - 1 : 0x7fffffff;
+        const int lim = kCausal ? (kRagged ? qlim : qrow)
+                        : kRagged ? S - 1
+                                  : 0x7fffffff;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
           const float pe = kglob > lim ? 0.f : p_elem(s[r], c1, lse2);
           ds[r] = ds_elem(pe, dpk(r), dvq, p.scale);
         }
-      } else if (kCausal ? kbase + 31 > qb : kRagged && kbase + 31 >= p.S) {
+      } else if ((kCausal && kbase + 31 > qb) ||
+                 (kRagged && kbase + 31 >= S)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kglob = kbase + crow(r, hi);
-          const float pe = (kCausal ? kglob > qrow : kglob >= p.S)
+          const float pe = key_masked<kCausal, kRagged>(kglob, qrow, qlim, S)
                                ? 0.f
                                : p_elem(s[r], c1, lse2);
           ds[r] = ds_elem(pe, dpk(r), dvq, p.scale);
@@ -618,7 +729,7 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
     cur ^= 1;
   }
 
-  if (kRagged && qrow >= p.S) return;  // stores only; no barrier follows
+  if (kRagged && qrow >= S) return;  // stores only; no barrier follows
   __bf16* drow = dqg + (long)qrow * p.dqs.ss;
 #pragma unroll
   for (int db = 0; db < 2; ++db) {
@@ -639,9 +750,10 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
 //   dV += P^T·dO   (A=packed P^T, B=dO^T tr frags)
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged, bool kDrop>
+template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
 __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
-  static_assert(!(kCausal && kRagged), "causal needs S % 128 == 0");
+  static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
+                "fixed-length causal needs S % 128 == 0; varlen is ragged");
   // 64-row q tiles, double-buffered: Q images, then dO images, then the
   // lse2/delta side tile (then the tiles' dropout q parts); the epilogue
   // reuses [0,32K) as per-wave f32 scratch for the coalesced dV/dK stores.
@@ -656,22 +768,35 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
-  const int kt = blockIdx.x;
-  const int bh = blockIdx.y;
-  const int b = bh / p.H, h = bh % p.H;
+  int kt = blockIdx.x, bh = blockIdx.y, b, h, S = p.S;  // as in the forward
+  long row0 = 0;
+  if constexpr (kVarlen) {
+    const VarlenTile vt = varlen_tile(p);
+    if (varlen_idle(vt)) return;
+    kt = vt.tile;
+    b = 0;
+    h = blockIdx.y;
+    bh = vt.seq * p.H + h;
+    S = vt.len;
+    row0 = vt.start;
+  } else {
+    b = bh / p.H;
+    h = bh % p.H;
+  }
 
-  const __bf16* qg = plane(p.q, p.qs, b, h);
-  const __bf16* kg = plane(p.k, p.ks, b, h);
-  const __bf16* vg = plane(p.v, p.vs, b, h);
-  const __bf16* dog = plane(p.dout, p.dos_, b, h);
-  __bf16* dkg = plane(p.dk, p.dks, b, h);
-  __bf16* dvg = plane(p.dv, p.dvs, b, h);
-  const float* lseg = p.lse + (long)bh * p.S;
-  const float* deltag = p.delta + (long)bh * p.S;
+  const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  const __bf16* dog = seq_plane<kVarlen>(p.dout, p.dos_, b, h, row0);
+  __bf16* dkg = seq_plane<kVarlen>(p.dk, p.dks, b, h, row0);
+  __bf16* dvg = seq_plane<kVarlen>(p.dv, p.dvs, b, h, row0);
+  const long lrow0 = kVarlen ? (long)h * p.total + row0 : (long)bh * S;
+  const float* lseg = p.lse + lrow0;
+  const float* deltag = p.delta + lrow0;
 
   const int kbb = kt * kQT + wave * 32;     // this wave's first k row
   const int krow = kbb + (lane & 31);       // this lane's k row
-  const long kld = ld_row32<kRagged>(krow, p.S);
+  const long kld = ld_row32<kRagged>(krow, S);
 
   // K and V^T B-fragments direct from global: lane holds
   // K[krow][chunk*16+8*hi+e] / V[krow][...]
@@ -689,8 +814,10 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
-  const int t0 = kCausal ? kt : 0;          // first 64-row q tile
-  const int n64 = (p.S + 63) / 64;
+  // first 64-row q tile (varlen starts at the diagonal itself: the tiles
+  // between kt and it are skipped whole by the causal cut below)
+  const int t0 = kCausal ? (kVarlen ? kt * (kQT / 64) : kt) : 0;
+  const int n64 = (S + 63) / 64;
 
   // dropout: this lane's k part; seed_lo feeds the tiles' q parts
   [[maybe_unused]] unsigned dkb = 0, seed_lo = 0;
@@ -703,12 +830,12 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   // stage q/dO tile t0 and its side tile
   {
     const int qb0 = t0 * 64;
-    const long r0 = ld_row32<kRagged>(qb0 + srow, p.S);
-    const long r1 = ld_row32<kRagged>(qb0 + srow + 32, p.S);
+    const long r0 = ld_row32<kRagged>(qb0 + srow, S);
+    const long r1 = ld_row32<kRagged>(qb0 + srow + 32, S);
     st_pair(img(qimg, 0), srow, scol, ld_pair(qg, p.qs.ss, r0, r1, scol));
     st_pair(img(doimg, 0), srow, scol, ld_pair(dog, p.dos_.ss, r0, r1, scol));
     if (threadIdx.x < 64) {
-      const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, p.S);
+      const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, S);
       st_side(side, 0, threadIdx.x, ld_side(lseg, deltag, rq));
       if constexpr (kDrop)
         qpart[threadIdx.x] = drop_q_part(seed_lo, bh, qb0 + threadIdx.x);
@@ -723,12 +850,12 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
     const bool pref = t + 1 < n64;
     if (pref) {
       const int qb1 = (t + 1) * 64;
-      const long r0 = ld_row32<kRagged>(qb1 + srow, p.S);
-      const long r1 = ld_row32<kRagged>(qb1 + srow + 32, p.S);
+      const long r0 = ld_row32<kRagged>(qb1 + srow, S);
+      const long r1 = ld_row32<kRagged>(qb1 + srow + 32, S);
       nq = ld_pair(qg, p.qs.ss, r0, r1, scol);
       nd = ld_pair(dog, p.dos_.ss, r0, r1, scol);
       if (threadIdx.x < 64) {
-        const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, p.S);
+        const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, S);
         ns = ld_side(lseg, deltag, rq);
         if constexpr (kDrop)
           part_buf(qpart, cur ^ 1)[threadIdx.x] =
@@ -741,9 +868,10 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
       const int qbase = t * 64 + half * 32;
       if (kCausal) {
         if (qbase + 31 < kbb) continue;     // wave-uniform causal cut
-      } else if (kRagged) {
+      }
+      if (kRagged) {
         // wave-uniform: a q half-tile or a k-row wave that is all padding
-        if (qbase >= p.S || kbb >= p.S) break;
+        if (qbase >= S || kbb >= S) break;
       }
       const char* qi = img(qimg, cur) + half * kHalfImg;
       const char* di = img(doimg, cur) + half * kHalfImg;
@@ -771,12 +899,13 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
           dp[r] = keep[r] ? dp[r] * p.drop_rp : 0.f;
         }
       }
-      if (kCausal ? qbase < kbb + 31 : kRagged && qbase + 31 >= p.S) {
-        // diagonal: mask q < k; ragged: mask the q rows past S-1
+      if ((kCausal && qbase < kbb + 31) || (kRagged && qbase + 31 >= S)) {
+        // diagonal: mask q < k; ragged: mask the q rows past S-1, which
+        // then add exact zeros to dK and dV (their P and dS are 0)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qglob = qbase + crow(r, hi);
-          pv[r] = (kCausal ? qglob < krow : qglob >= p.S)
+          pv[r] = ((kCausal && qglob < krow) || (kRagged && qglob >= S))
                       ? 0.f
                       : p_elem(sacc[r], c1, lsec[crow(r, hi)]);
           ds[r] = ds_elem(pv[r], dp[r], dc[crow(r, hi)], p.scale);
@@ -851,7 +980,7 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 #pragma unroll
     for (int mq = 0; mq < 8; ++mq) {
       const float* src = scratch + row * 64 + dhalf + mq * 4;
-      if (!kRagged || kbb + row < p.S)
+      if (!kRagged || kbb + row < S)
         store4_bf16(outg + (long)(kbb + row) * os.ss + dhalf + mq * 4, src[0],
                     src[1], src[2], src[3]);
     }
@@ -872,6 +1001,81 @@ __global__ __launch_bounds__(256) void fa_dropout_mask_kernel(
   const unsigned bh = blockIdx.y;
   out[bh * n + i] =
       drop_keep(*seed, bh, (unsigned)(i / S), (unsigned)(i % S), thr);
+}
+
+// ---------------------------------------------------------------------------
+// The variable-length plan: cu_seqlens (n_seqs + 1 row offsets) -> the tile
+// map of FaParams::tmap, on the device, so a launch never waits for the
+// host to read the offsets. One workgroup.
+//
+// Sequence i is rows [e_i, e_{i+1}) with e_i = clamp(max(cu[0..i]), 0,
+// total). For a well-formed vector (non-decreasing, cu[0] = 0, cu[n] =
+// total) that is cu itself. For any other it is still a non-decreasing
+// chain inside [0, total]: the sequences are disjoint, in range, and their
+// lengths sum to at most total, so they have at most total/128 + n_seqs
+// tiles, the size of the map and of the launches that index it. A sequence
+// that comes out empty gets no tile. Entries past the last tile are -1.
+//
+// Thread t owns a run of consecutive sequences; two block scans carry the
+// running maximum and the tile count across the runs.
+// ---------------------------------------------------------------------------
+constexpr int kIntMin = -2147483647 - 1;
+
+// Exclusive scan of x over the block's 256 threads, max or sum; *all gets
+// the reduction over all of them.
+template <bool kMax>
+__device__ __forceinline__ int plan_scan(int* buf, int x, int* all) {
+  const int t = threadIdx.x;
+  constexpr int kId = kMax ? kIntMin : 0;
+  buf[t] = x;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int y = t >= d ? buf[t - d] : kId;
+    __syncthreads();
+    buf[t] = kMax ? max(buf[t], y) : buf[t] + y;
+    __syncthreads();
+  }
+  const int excl = t ? buf[t - 1] : kId;
+  *all = buf[255];
+  __syncthreads();
+  return excl;
+}
+
+__device__ __forceinline__ int clamp_row(int x, int total) {
+  return min(max(x, 0), total);
+}
+
+__global__ __launch_bounds__(256) void fa_varlen_plan_kernel(
+    const int* cu, int n_seqs, int total, int max_tiles, int4* tmap) {
+  __shared__ int buf[256];
+  const int t = threadIdx.x;
+  const int per = (n_seqs + 255) / 256;
+  const int i0 = min(t * per, n_seqs), i1 = min(i0 + per, n_seqs);
+
+  // running maximum in front of this thread's first sequence
+  int mx = kIntMin;
+  for (int i = i0; i < i1; ++i) mx = max(mx, cu[i + 1]);
+  int unused;
+  const int m0 = max(cu[0], plan_scan<true>(buf, mx, &unused));
+
+  int tiles = 0;
+  for (int i = i0, m = m0; i < i1; ++i) {
+    const int e = clamp_row(m, total);
+    m = max(m, cu[i + 1]);
+    tiles += (clamp_row(m, total) - e + kQT - 1) / kQT;
+  }
+  int n_tiles;
+  int at = plan_scan<false>(buf, tiles, &n_tiles);
+
+  for (int i = i0, m = m0; i < i1; ++i) {
+    const int e = clamp_row(m, total);
+    m = max(m, cu[i + 1]);
+    const int len = clamp_row(m, total) - e;
+    for (int j = 0; j * kQT < len; ++j, ++at)
+      if (at < max_tiles) tmap[at] = make_int4(i, j, e, len);
+  }
+  for (int x = n_tiles + t; x < max_tiles; x += 256)
+    tmap[x] = make_int4(-1, -1, -1, -1);
 }
 
 // ---------------------------------------------------------------------------
@@ -909,17 +1113,36 @@ void check_len(const char* name, int S, bool causal) {
                              ": causal needs S % 128 == 0");
 }
 
-// Calls f(kCausal, kRagged, kDrop) with the mode as three
-// std::bool_constant values.
+void check_varlen(const char* name, int total, int n_seqs, int H) {
+  if (total < 1) throw std::runtime_error(std::string(name) + ": total < 1");
+  if (n_seqs < 1)
+    throw std::runtime_error(std::string(name) + ": n_seqs < 1");
+  if (H < 1) throw std::runtime_error(std::string(name) + ": H < 1");
+  if ((long)total / kQT + n_seqs > 0x7fffffffL - kQT || total > 0x7fffff00)
+    throw std::runtime_error(std::string(name) + ": too many tiles");
+}
+
+// Entries of the tile map, and workgroups in x of a variable-length launch.
+int varlen_max_tiles(int total, int n_seqs) { return total / kQT + n_seqs; }
+
+// Calls f(kCausal, kRagged, kDrop, kVarlen) with the mode as four
+// std::bool_constant values. The variable-length mode is always ragged, and
+// S means nothing to it.
 template <typename F>
-void with_mode(bool causal, int S, bool drop, F&& f) {
+void with_mode(bool causal, int S, bool drop, bool varlen, F&& f) {
   auto g = [&](auto d) {
-    if (causal)
-      f(std::true_type{}, std::false_type{}, d);
-    else if (S % kQT == 0)
-      f(std::false_type{}, std::false_type{}, d);
-    else
-      f(std::false_type{}, std::true_type{}, d);
+    if (varlen) {
+      if (causal)
+        f(std::true_type{}, std::true_type{}, d, std::true_type{});
+      else
+        f(std::false_type{}, std::true_type{}, d, std::true_type{});
+    } else if (causal) {
+      f(std::true_type{}, std::false_type{}, d, std::false_type{});
+    } else if (S % kQT == 0) {
+      f(std::false_type{}, std::false_type{}, d, std::false_type{});
+    } else {
+      f(std::false_type{}, std::true_type{}, d, std::false_type{});
+    }
   };
   if (drop)
     g(std::true_type{});
@@ -948,6 +1171,48 @@ FaParams fwd_params(const void* q, const void* k, const void* v, void* o,
   return p;
 }
 
+// The backward's part. strides 4..7: dO, dq, dk, dv.
+void bwd_params(FaParams& p, const void* do_, float* delta, void* dq,
+                void* dk, void* dv, const long* strides) {
+  p.dout = (const __bf16*)do_;
+  p.delta = delta;
+  p.dq = (__bf16*)dq;
+  p.dk = (__bf16*)dk;
+  p.dv = (__bf16*)dv;
+  p.dos_ = stride_at(strides, 4);
+  p.dqs = stride_at(strides, 5);
+  p.dks = stride_at(strides, 6);
+  p.dvs = stride_at(strides, 7);
+}
+
+void set_varlen(FaParams& p, const int* tmap, int total) {
+  if (tmap == nullptr) throw std::runtime_error("fa_varlen: no tile map");
+  p.tmap = reinterpret_cast<const int4*>(tmap);
+  p.total = total;
+}
+
+void launch_fwd(const FaParams& p, dim3 grid, bool causal, bool drop,
+                bool varlen, hipStream_t stream) {
+  with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                   kD = decltype(d)::value, kV = decltype(vl)::value;
+    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR, kD, kV>), grid, dim3(256), 0,
+                       stream, p);
+  });
+}
+
+void launch_bwd(const FaParams& p, dim3 grid, bool causal, bool drop,
+                bool varlen, hipStream_t stream) {
+  with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
+    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                   kD = decltype(d)::value, kV = decltype(vl)::value;
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR, kD, kV>), grid, dim3(256),
+                       0, stream, p);
+    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR, kD, kV>), grid, dim3(256),
+                       0, stream, p);
+  });
+}
+
 }  // namespace
 
 // drop_threshold for the other users of attn_drop.h's mask (lnorm.hip).
@@ -968,12 +1233,7 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
   FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
   set_drop(p, dropout_p, seed);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  with_mode(causal, S, dropout_p > 0.0, [&](auto c, auto r, auto d) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                   kD = decltype(d)::value;
-    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR, kD>), grid, dim3(256), 0,
-                       stream, p);
-  });
+  launch_fwd(p, grid, causal, dropout_p > 0.0, false, stream);
 }
 
 // strides: q, k, v, o, dO, dq, dk, dv. delta is a [B,H,S] f32 workspace the
@@ -988,24 +1248,57 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
   FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
                           const_cast<float*>(lse), H, S, strides, scale);
   set_drop(p, dropout_p, seed);
-  p.dout = (const __bf16*)do_;
-  p.delta = delta;
-  p.dq = (__bf16*)dq;
-  p.dk = (__bf16*)dk;
-  p.dv = (__bf16*)dv;
-  p.dos_ = stride_at(strides, 4);
-  p.dqs = stride_at(strides, 5);
-  p.dks = stride_at(strides, 6);
-  p.dvs = stride_at(strides, 7);
+  bwd_params(p, do_, delta, dq, dk, dv, strides);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  with_mode(causal, S, dropout_p > 0.0, [&](auto c, auto r, auto d) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                   kD = decltype(d)::value;
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR, kD>), grid, dim3(256), 0,
-                       stream, p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR, kD>), grid, dim3(256), 0,
-                       stream, p);
-  });
+  launch_bwd(p, grid, causal, dropout_p > 0.0, false, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Variable-length launchers. Tensors are [total, H, 64] views (strides as
+// above with the batch stride unused), lse and delta fp32 [H, total], tmap
+// the int32 [total/128 + n_seqs, 4] map that fa_varlen_plan filled on the
+// same stream. Nothing here reads cu_seqlens or the map on the host.
+// ---------------------------------------------------------------------------
+void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
+                    hipStream_t stream) {
+  check_varlen("fa_varlen_plan", total, n_seqs, 1);
+  if (cu_seqlens == nullptr || tmap == nullptr)
+    throw std::runtime_error("fa_varlen_plan: null pointer");
+  hipLaunchKernelGGL(fa_varlen_plan_kernel, dim3(1), dim3(256), 0, stream,
+                     cu_seqlens, n_seqs, total,
+                     varlen_max_tiles(total, n_seqs),
+                     reinterpret_cast<int4*>(tmap));
+}
+
+void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
+                       float* lse, const int* tmap, int total, int n_seqs,
+                       int H, const long* strides, float scale,
+                       hipStream_t stream, bool causal, double dropout_p,
+                       const long* seed) {
+  check_varlen("fa_varlen_forward", total, n_seqs, H);
+  check_drop("fa_varlen_forward", dropout_p, seed);
+  FaParams p = fwd_params(q, k, v, o, lse, H, 0, strides, scale);
+  set_drop(p, dropout_p, seed);
+  set_varlen(p, tmap, total);
+  const dim3 grid(varlen_max_tiles(total, n_seqs), H);
+  launch_fwd(p, grid, causal, dropout_p > 0.0, true, stream);
+}
+
+void fa_varlen_backward(const void* q, const void* k, const void* v,
+                        const void* o, const void* do_, const float* lse,
+                        float* delta, void* dq, void* dk, void* dv,
+                        const int* tmap, int total, int n_seqs, int H,
+                        const long* strides, float scale, hipStream_t stream,
+                        bool causal, double dropout_p, const long* seed) {
+  check_varlen("fa_varlen_backward", total, n_seqs, H);
+  check_drop("fa_varlen_backward", dropout_p, seed);
+  FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
+                          const_cast<float*>(lse), H, 0, strides, scale);
+  set_drop(p, dropout_p, seed);
+  set_varlen(p, tmap, total);
+  bwd_params(p, do_, delta, dq, dk, dv, strides);
+  const dim3 grid(varlen_max_tiles(total, n_seqs), H);
+  launch_bwd(p, grid, causal, dropout_p > 0.0, true, stream);
 }
 
 // out: [B,H,S,S] bytes, 1 where the element is kept.

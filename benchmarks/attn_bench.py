@@ -1,11 +1,17 @@
 """Flash-attention kernel timing: hand-written CDNA4 kernels vs torch SDPA.
 
-Run on a GPU box:  python benchmarks/attn_bench.py [--shape gpt2|vit]
+Run on a GPU box:  python benchmarks/attn_bench.py [--shape gpt2|vit|varlen]
                                                    [--dropout P]
 
 gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
 (ViT-base at 224 px). --dropout P times both paths with attention dropout at
 rate P (ours inside the kernels, a fresh seed drawn per call as in training).
+varlen: 131072 tokens of H12 D64 causal packed sequences through
+flash_attention_qkv_varlen, first as 128 sequences of 1024 against the
+fixed-length packed kernel on the same work (the cost of the mode), then as
+a seeded mix of lengths drawn log-uniformly in [16, 1024] against the same
+documents padded to 1024 and against SDPA under a dense block-diagonal mask
+(what the mode is for), and the plan kernel by itself.
 """
 import argparse
 import math
@@ -39,7 +45,8 @@ def main():
     from adapcc_amd.ops.attention import fa_supported, flash_attention
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", choices=sorted(SHAPES), default="gpt2")
+    ap.add_argument("--shape", choices=sorted(SHAPES) + ["varlen"],
+                    default="gpt2")
     ap.add_argument("--iters", type=int, default=None,
                     help="timed calls per figure (default 20; 200 for vit, "
                          "whose calls are ~10x shorter)")
@@ -47,6 +54,8 @@ def main():
                     help="attention dropout rate for both paths")
     args = ap.parse_args()
     drop = args.dropout
+    if args.shape == "varlen":
+        return varlen_path(args.iters or 20, drop)
     B, H, S, D, causal = SHAPES[args.shape]
     iters = args.iters or (200 if args.shape == "vit" else 20)
 
@@ -110,6 +119,127 @@ def layer_path(B, H, S, D, causal, fwd_flops, bwd_flops, iters, drop=0.0):
 
         ms = bench(fb, iters)
         print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
+
+
+def _fwd_and_fb(name, f, x, gy, iters):
+    """Times f(x) and f(x).backward(gy); returns (fwd ms, fwd+bwd ms)."""
+    fwd = bench(lambda: f(x), iters)
+
+    def fb():
+        x.grad = None
+        f(x).backward(gy)
+
+    both = bench(fb, iters)
+    print(f"{name} fwd:  {fwd:7.3f} ms   f+b:  {both:7.3f} ms")
+    return fwd, both
+
+
+def mixed_lengths(tokens, lo, hi, seed):
+    """Seeded lengths, log-uniform in [lo, hi], that sum to `tokens` (the
+    last one cut to fit)."""
+    gen = torch.Generator().manual_seed(seed)
+    lens, left = [], tokens
+    while left > 0:
+        u = torch.rand((), generator=gen).item()
+        span = math.log(hi) - math.log(lo)
+        n = int(round(math.exp(math.log(lo) + u * span)))
+        n = min(max(n, lo), hi, left)
+        lens.append(n)
+        left -= n
+    return lens
+
+
+def varlen_path(iters, drop=0.0, tokens=131072, H=12, D=64, S=1024):
+    from adapcc_amd.ops.attention import (_varlen_plan,
+                                          fa_qkv_varlen_supported,
+                                          flash_attention_qkv,
+                                          flash_attention_qkv_varlen)
+
+    C = H * D
+    torch.manual_seed(0)
+
+    def cu_of(lens):
+        cu = torch.tensor([0] + lens, dtype=torch.int64).cumsum(0)
+        return cu.to(torch.int32).cuda()
+
+    def make(rows):
+        x = torch.randn(rows, 3 * C, device="cuda", dtype=torch.bfloat16,
+                        requires_grad=True)
+        return x, torch.randn(rows, C, device="cuda", dtype=torch.bfloat16)
+
+    # 1. the cost of the mode: identical work, both ways
+    n = tokens // S
+    cu = cu_of([S] * n)
+    x, gy = make(tokens)
+    assert fa_qkv_varlen_supported(x, H, cu, drop)
+    print(f"uniform: {n} sequences of {S}, H{H} D{D}, causal")
+    vf, vb = _fwd_and_fb(
+        "varlen packed      ",
+        lambda t: flash_attention_qkv_varlen(t, H, cu, dropout_p=drop),
+        x, gy, iters)
+    x3 = x.detach().view(n, S, 3 * C).requires_grad_(True)
+    ff, fb = _fwd_and_fb(
+        "fixed-length packed",
+        lambda t: flash_attention_qkv(t, H, dropout_p=drop),
+        x3, gy.view(n, S, C), iters)
+    print(f"varlen / fixed: fwd {vf / ff:.3f}  f+b {vb / fb:.3f}")
+
+    # 2. what the mode is for: mixed lengths, no padding
+    lens = mixed_lengths(tokens, 16, S, seed=0)
+    n = len(lens)
+    tiles = [-(-m // 128) for m in lens]
+    full = (S // 128) * (S // 128 + 1) // 2
+    work = sum(t * (t + 1) // 2 for t in tiles) / (n * full)
+    print(f"mixed: {n} sequences, lengths {min(lens)}..{max(lens)}, "
+          f"{tokens} tokens; padded to {S}: {n * S} tokens")
+    print(f"work ratio (tile pairs, varlen / padded): {work:.3f}")
+    cu = cu_of(lens)
+    vf, vb = _fwd_and_fb(
+        "varlen packed      ",
+        lambda t: flash_attention_qkv_varlen(t, H, cu, dropout_p=drop),
+        x, gy, iters)
+    xp, gp = make(n * S)
+    pf, pb = _fwd_and_fb(
+        "padded fixed-length",
+        lambda t: flash_attention_qkv(t, H, dropout_p=drop),
+        xp.detach().view(n, S, 3 * C).requires_grad_(True),
+        gp.view(n, S, C), iters)
+    print(f"varlen / padded: fwd {vf / pf:.3f}  f+b {vb / pb:.3f}  "
+          f"(work ratio {work:.3f})")
+    del xp, gp
+
+    # SDPA under the dense block-diagonal mask, at a size whose mask fits:
+    # the first documents, up to 8192 tokens
+    sub, rows = [], 0
+    for m in lens:
+        if rows + m > 8192:
+            break
+        sub.append(m)
+        rows += m
+    cu_s = cu_of(sub)
+    xs, gs = make(rows)
+    doc = torch.repeat_interleave(torch.arange(len(sub), device="cuda"),
+                                  torch.tensor(sub, device="cuda"))
+    mask = (doc.view(-1, 1) == doc.view(1, -1)).tril_()
+
+    def sdpa(t):
+        q, k, v = (u.view(1, rows, H, D).transpose(1, 2)
+                   for u in t.split(C, dim=1))
+        y = torch.nn.functional.scaled_dot_product_attention(
+            q, k, v, attn_mask=mask, dropout_p=drop)
+        return y.transpose(1, 2).reshape(rows, C)
+
+    print(f"subset for SDPA: {len(sub)} sequences, {rows} tokens")
+    sv = _fwd_and_fb(
+        "varlen packed      ",
+        lambda t: flash_attention_qkv_varlen(t, H, cu_s, dropout_p=drop),
+        xs, gs, iters)
+    sd = _fwd_and_fb("SDPA dense mask    ", sdpa, xs, gs, iters)
+    print(f"varlen / SDPA: fwd {sv[0] / sd[0]:.3f}  f+b {sv[1] / sd[1]:.3f}")
+
+    ms = bench(lambda: _varlen_plan(cu, tokens), 200)
+    print(f"plan kernel alone ({n} sequences, with its output "
+          f"allocation): {ms * 1e3:7.1f} us")
 
 
 if __name__ == "__main__":
