@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops.attention import flash_attention_qkv
 from ..ops.fused import FusedLayerNorm
 from ..ops.moe import (moe_combine, moe_dispatch, moe_fusable, moe_route_top1,
                        moe_route_topk)
@@ -213,18 +214,39 @@ class MoEMLP(nn.Module):
 
 class MoETransformerBlock(nn.Module):
     """Pre-norm block with MoE MLP (the reference's FMoETransformerMLP
-    stand-in for workload tests)."""
+    stand-in for workload tests).
 
-    def __init__(self, d_model: int = 1024, n_head: int = 8, **moe_kw):
+    ``fused_attention=True`` keeps the same ``nn.MultiheadAttention`` module
+    (same parameters, same ``state_dict``) and computes it as in-projection,
+    ``flash_attention_qkv`` on the packed projection, out-projection: the MHA
+    in-projection lays out q, k, v as thirds with the heads contiguous inside
+    each, the layout the flash-attention kernels read in place. In bf16 on
+    the GPU with ``d_model / n_head`` 64 or 128 that runs the CDNA4 kernels;
+    elsewhere ``flash_attention_qkv`` composes the same function from torch
+    SDPA."""
+
+    def __init__(self, d_model: int = 1024, n_head: int = 8,
+                 fused_attention: bool = False, **moe_kw):
         super().__init__()
         self.ln1 = FusedLayerNorm(d_model)
         self.attn = nn.MultiheadAttention(d_model, n_head, batch_first=True)
         self.ln2 = FusedLayerNorm(d_model)
         self.moe = MoEMLP(d_model=d_model, **moe_kw)
+        self.fused_attention = fused_attention
+
+    def _attention(self, h: torch.Tensor) -> torch.Tensor:
+        attn = self.attn
+        if not self.fused_attention:
+            a, _ = attn(h, h, h, need_weights=False)
+            return a
+        qkv = F.linear(h, attn.in_proj_weight, attn.in_proj_bias)
+        y = flash_attention_qkv(
+            qkv, attn.num_heads, causal=False,
+            dropout_p=attn.dropout if self.training else 0.0)
+        return attn.out_proj(y)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         h = self.ln1(x)
-        a, _ = self.attn(h, h, h, need_weights=False)
-        x = x + a
+        x = x + self._attention(h)
         x = x + self.moe(self.ln2(x))
         return x

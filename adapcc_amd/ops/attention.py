@@ -1,8 +1,8 @@
 """Hand-written CDNA4 flash attention (csrc/attn.hip) with autograd.
 
-Supported fast paths, both bf16, head_dim 64, self-attention (q, k, v of one
-shape), attention dropout 0 <= p < 1: causal with seq len a multiple of 128
-(GPT-2), and non-causal with any seq len >= 1 (ViT: 197). Anything else
+Supported fast paths, both bf16, head_dim 64 or 128, self-attention (q, k, v
+of one shape), attention dropout 0 <= p < 1: causal with seq len a multiple
+of 128 (GPT-2), and non-causal with any seq len >= 1 (ViT: 197). Anything else
 falls back to torch SDPA. Tensors are [B, H, S, D] with any batch/head/row
 strides (rows must be contiguous and 16-B aligned), so the usual
 ``.view(B,T,H,hd).transpose(1,2)`` projection views work without a copy.
@@ -66,14 +66,14 @@ def _row_ok(t: torch.Tensor) -> bool:
 
 def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
                dropout_p: float) -> bool:
-    """What the kernels take, layout aside: bf16 on the GPU, head_dim 64,
-    S >= 1 (a multiple of 128 when causal), 0 <= dropout_p < 1, extension
-    built."""
+    """What the kernels take, layout aside: bf16 on the GPU, head_dim 64
+    or 128, S >= 1 (a multiple of 128 when causal), 0 <= dropout_p < 1,
+    extension built."""
     if not 0.0 <= dropout_p < 1.0:
         return False
     if not (t.is_cuda and t.dtype == torch.bfloat16):
         return False
-    if D != 64 or S < 1 or (causal and S % 128 != 0):
+    if D not in (64, 128) or S < 1 or (causal and S % 128 != 0):
         return False
     return bool(_core())
 
@@ -169,7 +169,8 @@ def _launch_fwd(q, k, v, o, lse, scale, causal=True, dropout_p=0.0,
     stream = torch.cuda.current_stream(q.device).cuda_stream
     _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    lse.data_ptr(), B, H, S, strides, scale, stream, causal,
-                   dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0)
+                   dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0,
+                   head_dim=q.shape[3])
 
 
 def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
@@ -191,7 +192,8 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
                    do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
                    strides, scale, stream, causal, dropout_p,
-                   seed.data_ptr() if dropout_p > 0.0 else 0)
+                   seed.data_ptr() if dropout_p > 0.0 else 0,
+                   head_dim=q.shape[3])
 
 
 def _fa_forward_lse(q, k, v, scale, causal, dropout_p=0.0, seed=None):
@@ -335,9 +337,9 @@ def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
                         ) -> torch.Tensor:
     """Self-attention on the packed projection qkv [B,T,3C] (q, k, v
     thirds, heads contiguous within each); returns [B,T,C]. The qualifying
-    case (bf16, head_dim 64, contiguous, dropout_p < 1; T a multiple of 128
-    when causal, any T >= 1 when not) runs the CDNA4 kernels directly on the
-    packed layout with no copies; anything else composes
+    case (bf16, head_dim 64 or 128, contiguous, dropout_p < 1; T a multiple
+    of 128 when causal, any T >= 1 when not) runs the CDNA4 kernels directly
+    on the packed layout with no copies; anything else composes
     ``flash_attention`` from views. dropout_seed as in ``flash_attention``."""
     if fa_qkv_supported(qkv, n_head, dropout_p, causal):
         scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
@@ -471,7 +473,8 @@ def _launch_varlen_fwd(q, k, v, o, lse, tmap, n_seqs, scale, causal=True,
                           o.data_ptr(), lse.data_ptr(), tmap.data_ptr(),
                           total, n_seqs, H, strides, scale, stream, causal,
                           dropout_p,
-                          seed.data_ptr() if dropout_p > 0.0 else 0)
+                          seed.data_ptr() if dropout_p > 0.0 else 0,
+                          head_dim=q.shape[3])
 
 
 def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
@@ -493,7 +496,8 @@ def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
                           delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
                           dv.data_ptr(), tmap.data_ptr(), total, n_seqs, H,
                           strides, scale, stream, causal, dropout_p,
-                          seed.data_ptr() if dropout_p > 0.0 else 0)
+                          seed.data_ptr() if dropout_p > 0.0 else 0,
+                          head_dim=q.shape[3])
 
 
 def _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale, causal,
@@ -615,7 +619,7 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     sequences are fine anywhere. A vector that breaks the contract gives
     unspecified values but no access outside the tensors.
 
-    bf16 on the GPU with D = 64 runs the CDNA4 kernels (any lengths, no
+    bf16 on the GPU with D = 64 or 128 runs the CDNA4 kernels (any lengths, no
     padding, no host sync; dropout mask plane seq * H + h with q and k
     counted from the sequence start); anything else runs torch SDPA under
     the block-diagonal mask, with torch's dropout."""
@@ -645,8 +649,8 @@ def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
                                ) -> torch.Tensor:
     """``flash_attention_varlen`` on the packed projection qkv [total,3C]
     (q, k, v thirds, heads contiguous within each); returns [total,C]. The
-    qualifying case (bf16, head_dim 64, contiguous, dropout_p < 1) runs the
-    kernels directly on the packed layout with no copies; anything else
+    qualifying case (bf16, head_dim 64 or 128, contiguous, dropout_p < 1)
+    runs the kernels directly on the packed layout with no copies; anything else
     composes ``flash_attention_varlen`` from views. cu_seqlens: see there."""
     if qkv.dim() != 2 or qkv.shape[1] % (3 * n_head):
         raise ValueError("flash_attention_qkv_varlen: qkv must be "

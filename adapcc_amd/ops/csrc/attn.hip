@@ -1,8 +1,8 @@
-// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim=64, in three
-// modes: causal with S % 128 == 0 (GPT-2), non-causal self-attention over
-// any S >= 1 (ViT: S = 197), and variable-length, causal or not, over
-// sequences of any lengths packed back to back in [total, H, 64] tensors
-// with cu_seqlens (GPT-2 on documents).
+// Hand-written CDNA4 flash attention (gfx950), bf16, head_dim 64 or 128, in
+// three modes: causal with S % 128 == 0 (GPT-2), non-causal self-attention
+// over any S >= 1 (ViT: S = 197), and variable-length, causal or not, over
+// sequences of any lengths packed back to back in [total, H, head_dim]
+// tensors with cu_seqlens (GPT-2 on documents).
 //
 // Replaces the stock SDPA path for the GPT-2 flagship workload, where the
 // aotriton kernels ran at ~2% of the MFMA roof (rocprof round-1 evidence:
@@ -21,8 +21,25 @@
 // backward splits FA2-style into a dq kernel (q-tile outer) and a dkv
 // kernel (kv-tile outer), both recomputing P from the saved logsumexp.
 //
-// The three kernels are templates on <kCausal, kRagged, kDrop, kVarlen>.
-// <true,false,false,false> is the GPT-2 case. kDrop adds attention dropout
+// The three kernels are templates on <kHD, kCausal, kRagged, kDrop, kVarlen>.
+// <64,true,false,false,false> is the GPT-2 case.
+// kHD is the head dimension, 64 or 128. A 128-wide row is two blocks of 64
+// columns and a 64-row tile two of attn_frag.h's row images side by side,
+// each with its own 128-byte-row swizzle, so every fragment read is the
+// 64-wide one at a block offset: S^T accumulates over kHD/16 chunks in
+// column order, O^T (dQ^T, dV, dK) is kHD/32 accumulators that share one P
+// (dS) and, in the forward, one rescale factor, and delta = rowsum(dO*O)
+// adds the two blocks' pairwise trees, lower block first. Staging moves
+// twice the bytes per tile (four 16-B loads per thread and tensor), LDS is
+// 64 KB per workgroup (65 KB in the dkv kernel, plus the dropout parts), and
+// the launch bounds follow: forward and dq 2 workgroups per CU (up to 256
+// VGPRs), dkv 1, since its two K/V operand sets and eight accumulators need
+// the AGPRs as well (no instantiation uses scratch). Mask, tile map, plan
+// and the causal, ragged, dropout and varlen logic do not depend on kHD,
+// and the kHD = 64 instantiations are instruction for instruction the
+// kernels from before the parameter: where a loop over blocks would do,
+// the blocks are spelled out under `if constexpr` for that reason.
+// kDrop adds attention dropout
 // on P (mask function in attn_drop.h): the forward zeroes dropped P after
 // the row sum, so the normaliser and lse are those of the undropped scores,
 // and folds 1/(1-p) into the epilogue's 1/rowsum; delta = rowsum(dO*O) needs no
@@ -110,7 +127,7 @@ struct FaParams {
   int total;           // packed rows; lse and delta are [H, total]
 };
 
-// Variable-length mode: q, k, v, ... are [total, H, 64] views that hold the
+// Variable-length mode: q, k, v, ... are [total, H, kHD] views that hold the
 // sequences back to back, and workgroup x of the launch owns the 128-row
 // tile `tile` of sequence `seq`, rows start .. start+len-1 of the packed
 // buffer, as the plan kernel (below) wrote it into tmap[x]. The kernels take
@@ -177,22 +194,52 @@ __device__ __forceinline__ bool key_masked(int kglob, int qrow, int qlim,
 }
 
 // ---------------------------------------------------------------------------
-// Staging: 256 threads cooperatively copy a [64][64] bf16 tile (8 KB) from
-// global (row stride `ss` elements) into an LDS image of two 32-row halves
-// (row_img_byte addresses within each half). Thread t moves the 16 B at
-// column scol = (t&7)*8 of rows srow = t>>3 and srow+32: two 16-B loads, held
-// in registers across the tile's compute, then two 16-B ds_writes.
+// Staging: 256 threads cooperatively copy a [64][kHD] bf16 tile (8 KB at
+// head_dim 64, 16 KB at 128) from global (row stride `ss` elements) into LDS.
+// A row is kHD/64 blocks of 64 columns, and each block of the tile is one
+// image of two 32-row halves (row_img_byte addresses within each half), the
+// blocks' images side by side: attn_frag.h's [32][64] row image and its
+// swizzle serve both widths. Thread t moves the 16 B at column scol =
+// (t&7)*8 of every block of rows srow = t>>3 and srow+32: two 16-B loads per
+// block, held in registers across the tile's compute, then as many 16-B
+// ds_writes.
 // ---------------------------------------------------------------------------
-constexpr int kHalfImg = 4096;       // one 32-row half
-constexpr int kImg = 2 * kHalfImg;   // one 64-row image
+constexpr int kHalfImg = 4096;       // one 32-row half of one column block
+constexpr int kImg = 2 * kHalfImg;   // one 64-row image of one column block
 
-// Image `buf` (0/1) of a double-buffered pair that starts at `base`.
+template <int kHD>
+constexpr int kTileImg = (kHD / 64) * kImg;  // one 64-row tile, all blocks
+
+// Tile image `buf` (0/1) of a double-buffered pair that starts at `base`.
+template <int kHD>
 __device__ __forceinline__ char* img(char* base, int buf) {
-  return base + buf * kImg;
+  return base + buf * kTileImg<kHD>;
+}
+
+// Fragment reads off a tile image (`im`: its 32-row half): 16-column chunk c
+// of the row, and 32-column block db of the transpose, each inside the
+// 64-column block that holds it. At head_dim 64 these are attn_frag.h's
+// reads themselves.
+template <int kHD>
+__device__ __forceinline__ bf16x8 read_row_chunk(const char* im, int lane,
+                                                 int c) {
+  if constexpr (kHD == 64)
+    return read_row_frag(im, lane, c);
+  else
+    return read_row_frag(im + (c >> 2) * kImg, lane, c & 3);
+}
+
+template <int kHD>
+__device__ __forceinline__ bf16x8 read_tr_blk(const char* im, int lane,
+                                              int kb, int db) {
+  if constexpr (kHD == 64)
+    return read_tr_frag(im, lane, kb, db);
+  else
+    return read_tr_frag(im + (db >> 1) * kImg, lane, kb, db & 1);
 }
 
 struct RowPair {
-  uint4 a, b;  // this thread's 16 B of rows srow and srow+32
+  uint4 a, b;  // this thread's 16 B of rows srow and srow+32, one block
 };
 
 // r0, r1: the (clamped) global rows that land in image rows srow, srow+32.
@@ -206,6 +253,30 @@ __device__ __forceinline__ void st_pair(char* im, int srow, int scol,
                                         const RowPair& x) {
   *reinterpret_cast<uint4*>(im + row_img_byte(srow, scol)) = x.a;
   *reinterpret_cast<uint4*>(im + kHalfImg + row_img_byte(srow, scol)) = x.b;
+}
+
+// The same for all kHD/64 column blocks of the rows. Spelled out per block,
+// not looped: the head_dim 64 kernels then compile to what they were before
+// the width became a parameter.
+template <int kHD>
+struct RowTile {
+  RowPair blk[kHD / 64];
+};
+
+template <int kHD>
+__device__ __forceinline__ RowTile<kHD> ld_tile(const __bf16* g, long ss,
+                                                long r0, long r1, int scol) {
+  RowTile<kHD> x;
+  x.blk[0] = ld_pair(g, ss, r0, r1, scol);
+  if constexpr (kHD == 128) x.blk[1] = ld_pair(g + 64, ss, r0, r1, scol);
+  return x;
+}
+
+template <int kHD>
+__device__ __forceinline__ void st_tile(char* im, int srow, int scol,
+                                        const RowTile<kHD>& x) {
+  st_pair(im, srow, scol, x.blk[0]);
+  if constexpr (kHD == 128) st_pair(im + kImg, srow, scol, x.blk[1]);
 }
 
 // The dkv kernel's side tile: lse*log2e and delta of a q tile's 64 rows, as
@@ -279,18 +350,23 @@ __device__ __forceinline__ float ds_elem(float pe, float dp, float delta,
 // Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
 // qt*128 + w*32 .. +31.
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
-__global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
+template <int kHD, bool kCausal, bool kRagged, bool kDrop,
+          bool kVarlen = false>
+__global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_fwd_kernel(
+    FaParams p) {
+  static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
   static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
                 "fixed-length causal needs S % 128 == 0; varlen is ragged");
+  constexpr int kNC = kHD / 16;  // 16-column chunks of a row
+  constexpr int kNB = kHD / 32;  // 32-column blocks: one accumulator each
   // 64-row KV tiles, double-buffered: K images, then V images (then the
   // tiles' dropout k parts).
   __shared__ __attribute__((aligned(16))) char
-      smem[4 * kImg + kPartBytes<kDrop>];
+      smem[4 * kTileImg<kHD> + kPartBytes<kDrop>];
   char* const kimg = smem;
-  char* const vimg = smem + 2 * kImg;
+  char* const vimg = smem + 2 * kTileImg<kHD>;
   [[maybe_unused]] unsigned* const kpart =
-      reinterpret_cast<unsigned*>(smem + 4 * kImg);
+      reinterpret_cast<unsigned*>(smem + 4 * kTileImg<kHD>);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -330,13 +406,16 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   // Q^T B-fragments, direct from global: lane l holds
   // Q[qrow][chunk*16 + 8*hi + e].
-  bf16x8 qf[4];
+  bf16x8 qf[kNC];
 #pragma unroll
-  for (int c = 0; c < 4; ++c)
+  for (int c = 0; c < kNC; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(
         qg + qld * p.qs.ss + c * 16 + hi * 8);
 
+  // O^T, one accumulator per 32 columns; acc2, acc3 (columns 64..127) are
+  // dead at head_dim 64
   f32x16 acc0 = {}, acc1 = {};
+  [[maybe_unused]] f32x16 acc2 = {}, acc3 = {};
   float m = kNegBig, ssum = 0.f;
   const float c1 = p.scale * kLog2e;
   float mc = m * c1;
@@ -363,8 +442,10 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   {
     const long r0 = ld_row<kRagged>((long)srow, S);
     const long r1 = ld_row<kRagged>((long)(srow + 32), S);
-    st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
-    st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(kimg, 0), srow, scol,
+                 ld_tile<kHD>(kg, p.ks.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(vimg, 0), srow, scol,
+                 ld_tile<kHD>(vg, p.vs.ss, r0, r1, scol));
     if constexpr (kDrop)
       if (threadIdx.x < 64)
         kpart[threadIdx.x] = drop_k_part(seed_hi, bh, threadIdx.x);
@@ -374,14 +455,14 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
   int cur = 0;
   for (int t = 0; t < n64; ++t) {
     // issue next tile's staging loads early; writes land after compute
-    RowPair nk, nv;
+    RowTile<kHD> nk, nv;
     const bool pref = t + 1 < n64;
     if (pref) {
       const long kb = (long)(t + 1) * 64 + srow;
       const long kb0 = ld_row<kRagged>(kb, S);
       const long kb1 = ld_row<kRagged>(kb + 32, S);
-      nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
-      nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
+      nk = ld_tile<kHD>(kg, p.ks.ss, kb0, kb1, scol);
+      nv = ld_tile<kHD>(vg, p.vs.ss, kb0, kb1, scol);
       if constexpr (kDrop)
         if (threadIdx.x < 64)
           part_buf(kpart, cur ^ 1)[threadIdx.x] =
@@ -398,15 +479,15 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
         // wave-uniform: a half-tile or a wave that is all padding
         if (kbase >= S || qb >= S) break;
       }
-      const char* ki = img(kimg, cur) + half * kHalfImg;
-      const char* vi = img(vimg, cur) + half * kHalfImg;
+      const char* ki = img<kHD>(kimg, cur) + half * kHalfImg;
+      const char* vi = img<kHD>(vimg, cur) + half * kHalfImg;
 
       // S^T tile: C[k][q] = sum_d K[k][d] * Q[q][d]
       f32x16 s = {};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-        s = mfma(read_row_frag(ki, lane, c), qf[c], s);
+      for (int c = 0; c < kNC; ++c)
+        s = mfma(read_row_chunk<kHD>(ki, lane, c), qf[c], s);
       __builtin_amdgcn_s_setprio(0);
 
       float pv[16];
@@ -440,6 +521,10 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
         for (int r = 0; r < 16; ++r) {
           acc0[r] *= alpha;
           acc1[r] *= alpha;
+          if constexpr (kNB == 4) {
+            acc2[r] *= alpha;
+            acc3[r] *= alpha;
+          }
         }
       }
 
@@ -468,16 +553,22 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
       // O^T += V^T · P^T  (A = V^T via hardware transpose reads)
       __builtin_amdgcn_s_setprio(1);
-      acc0 = mfma(read_tr_frag(vi, lane, 0, 0), p0, acc0);
-      acc0 = mfma(read_tr_frag(vi, lane, 1, 0), p1, acc0);
-      acc1 = mfma(read_tr_frag(vi, lane, 0, 1), p0, acc1);
-      acc1 = mfma(read_tr_frag(vi, lane, 1, 1), p1, acc1);
+      acc0 = mfma(read_tr_blk<kHD>(vi, lane, 0, 0), p0, acc0);
+      acc0 = mfma(read_tr_blk<kHD>(vi, lane, 1, 0), p1, acc0);
+      acc1 = mfma(read_tr_blk<kHD>(vi, lane, 0, 1), p0, acc1);
+      acc1 = mfma(read_tr_blk<kHD>(vi, lane, 1, 1), p1, acc1);
+      if constexpr (kNB == 4) {
+        acc2 = mfma(read_tr_blk<kHD>(vi, lane, 0, 2), p0, acc2);
+        acc2 = mfma(read_tr_blk<kHD>(vi, lane, 1, 2), p1, acc2);
+        acc3 = mfma(read_tr_blk<kHD>(vi, lane, 0, 3), p0, acc3);
+        acc3 = mfma(read_tr_blk<kHD>(vi, lane, 1, 3), p1, acc3);
+      }
       __builtin_amdgcn_s_setprio(0);
     }
 
     if (pref) {
-      st_pair(img(kimg, cur ^ 1), srow, scol, nk);
-      st_pair(img(vimg, cur ^ 1), srow, scol, nv);
+      st_tile<kHD>(img<kHD>(kimg, cur ^ 1), srow, scol, nk);
+      st_tile<kHD>(img<kHD>(vimg, cur ^ 1), srow, scol, nv);
     }
     __syncthreads();
     cur ^= 1;
@@ -493,8 +584,8 @@ __global__ __launch_bounds__(256, 3) void fa_fwd_kernel(FaParams p) {
 
   __bf16* orow = og + (long)qrow * p.os.ss;
 #pragma unroll
-  for (int db = 0; db < 2; ++db) {
-    const f32x16& a = db ? acc1 : acc0;
+  for (int db = 0; db < kNB; ++db) {
+    const f32x16& a = db == 3 ? acc3 : db == 2 ? acc2 : db ? acc1 : acc0;
 #pragma unroll
     for (int mq = 0; mq < 4; ++mq)
       store4_bf16(orow + db * 32 + 8 * mq + 4 * hi, a[4 * mq] * inv,
@@ -539,18 +630,23 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
   return (pr[0] + pr[1]) + (pr[2] + pr[3]);
 }
 
-template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
-__global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
+template <int kHD, bool kCausal, bool kRagged, bool kDrop,
+          bool kVarlen = false>
+__global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_bwd_dq_kernel(
+    FaParams p) {
+  static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
   static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
                 "fixed-length causal needs S % 128 == 0; varlen is ragged");
+  constexpr int kNC = kHD / 16;  // 16-column chunks of a row
+  constexpr int kNB = kHD / 32;  // 32-column blocks: one accumulator each
   // 64-row KV tiles, double-buffered: K images, then V images (then the
   // tiles' dropout k parts).
   __shared__ __attribute__((aligned(16))) char
-      smem[4 * kImg + kPartBytes<kDrop>];
+      smem[4 * kTileImg<kHD> + kPartBytes<kDrop>];
   char* const kimg = smem;
-  char* const vimg = smem + 2 * kImg;
+  char* const vimg = smem + 2 * kTileImg<kHD>;
   [[maybe_unused]] unsigned* const kpart =
-      reinterpret_cast<unsigned*>(smem + 4 * kImg);
+      reinterpret_cast<unsigned*>(smem + 4 * kTileImg<kHD>);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -585,14 +681,14 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   const long qld = ld_row32<kRagged>(qrow, S);
   [[maybe_unused]] const int qlim = min(qrow, S - 1);  // see the forward
 
-  // this lane holds 32 of its q row's 64 dO (and O) elements as four runs
-  // of 8 (columns c*16 + hi*8 ..); lane^32 holds the runs in between. n16[c]
-  // joins each run with its neighbour from the partner lane, so both lanes
-  // walk the same adjacent-pair tree over the whole row.
-  bf16x8 qf[4], dof[4];
-  float n16[4];
+  // this lane holds half of its q row's kHD dO (and O) elements as kHD/16
+  // runs of 8 (columns c*16 + hi*8 ..); lane^32 holds the runs in between.
+  // n16[c] joins each run with its neighbour from the partner lane, so both
+  // lanes walk the same adjacent-pair tree over the whole row.
+  bf16x8 qf[kNC], dof[kNC];
+  float n16[kNC];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
+  for (int c = 0; c < kNC; ++c) {
     dof[c] = *reinterpret_cast<const bf16x8*>(
         dog + qld * p.dos_.ss + c * 16 + hi * 8);
     const float n8 = dot8_tree(
@@ -601,16 +697,21 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
     n16[c] = n8 + __shfl_xor(n8, 32, 64);
   }
 #pragma unroll
-  for (int c = 0; c < 4; ++c)
+  for (int c = 0; c < kNC; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(
         qg + qld * p.qs.ss + c * 16 + hi * 8);
   const float lse2 = p.lse[lrow0 + qld] * kLog2e;
-  const float dvq = (n16[0] + n16[1]) + (n16[2] + n16[3]);
+  // the tree's top: 64-column blocks, then (head_dim 128) the two blocks
+  float dvq = (n16[0] + n16[1]) + (n16[2] + n16[3]);
+  if constexpr (kHD == 128)
+    dvq = dvq + ((n16[4] + n16[5]) + (n16[6] + n16[7]));
   if (hi == 0 && (!kRagged || qrow < S))
     p.delta[lrow0 + qrow] = dvq;
   const float c1 = p.scale * kLog2e;
 
+  // dQ^T, one accumulator per 32 columns (dacc2, dacc3: head_dim 128)
   f32x16 dacc0 = {}, dacc1 = {};
+  [[maybe_unused]] f32x16 dacc2 = {}, dacc3 = {};
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
@@ -626,8 +727,10 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   {
     const long r0 = ld_row32<kRagged>(srow, S);
     const long r1 = ld_row32<kRagged>(srow + 32, S);
-    st_pair(img(kimg, 0), srow, scol, ld_pair(kg, p.ks.ss, r0, r1, scol));
-    st_pair(img(vimg, 0), srow, scol, ld_pair(vg, p.vs.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(kimg, 0), srow, scol,
+                 ld_tile<kHD>(kg, p.ks.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(vimg, 0), srow, scol,
+                 ld_tile<kHD>(vg, p.vs.ss, r0, r1, scol));
     if constexpr (kDrop)
       if (threadIdx.x < 64)
         kpart[threadIdx.x] = drop_k_part(seed_hi, bh, threadIdx.x);
@@ -636,13 +739,13 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
 
   int cur = 0;
   for (int t = 0; t < n64; ++t) {
-    RowPair nk, nv;
+    RowTile<kHD> nk, nv;
     const bool pref = t + 1 < n64;
     if (pref) {
       const long kb0 = ld_row32<kRagged>((t + 1) * 64 + srow, S);
       const long kb1 = ld_row32<kRagged>((t + 1) * 64 + srow + 32, S);
-      nk = ld_pair(kg, p.ks.ss, kb0, kb1, scol);
-      nv = ld_pair(vg, p.vs.ss, kb0, kb1, scol);
+      nk = ld_tile<kHD>(kg, p.ks.ss, kb0, kb1, scol);
+      nv = ld_tile<kHD>(vg, p.vs.ss, kb0, kb1, scol);
       if constexpr (kDrop)
         if (threadIdx.x < 64)
           part_buf(kpart, cur ^ 1)[threadIdx.x] =
@@ -658,15 +761,15 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
       if (kRagged) {
         if (kbase >= S || qb >= S) break;  // all padding
       }
-      const char* ki = img(kimg, cur) + half * kHalfImg;
-      const char* vi = img(vimg, cur) + half * kHalfImg;
+      const char* ki = img<kHD>(kimg, cur) + half * kHalfImg;
+      const char* vi = img<kHD>(vimg, cur) + half * kHalfImg;
 
       f32x16 s = {}, dp = {};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        s = mfma(read_row_frag(ki, lane, c), qf[c], s);
-        dp = mfma(read_row_frag(vi, lane, c), dof[c], dp);
+      for (int c = 0; c < kNC; ++c) {
+        s = mfma(read_row_chunk<kHD>(ki, lane, c), qf[c], s);
+        dp = mfma(read_row_chunk<kHD>(vi, lane, c), dof[c], dp);
       }
       __builtin_amdgcn_s_setprio(0);
 
@@ -714,16 +817,22 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
       const bf16x8 d0 = pack_frag(&ds[0]);
       const bf16x8 d1 = pack_frag(&ds[8]);
       __builtin_amdgcn_s_setprio(1);
-      dacc0 = mfma(read_tr_frag(ki, lane, 0, 0), d0, dacc0);
-      dacc0 = mfma(read_tr_frag(ki, lane, 1, 0), d1, dacc0);
-      dacc1 = mfma(read_tr_frag(ki, lane, 0, 1), d0, dacc1);
-      dacc1 = mfma(read_tr_frag(ki, lane, 1, 1), d1, dacc1);
+      dacc0 = mfma(read_tr_blk<kHD>(ki, lane, 0, 0), d0, dacc0);
+      dacc0 = mfma(read_tr_blk<kHD>(ki, lane, 1, 0), d1, dacc0);
+      dacc1 = mfma(read_tr_blk<kHD>(ki, lane, 0, 1), d0, dacc1);
+      dacc1 = mfma(read_tr_blk<kHD>(ki, lane, 1, 1), d1, dacc1);
+      if constexpr (kNB == 4) {
+        dacc2 = mfma(read_tr_blk<kHD>(ki, lane, 0, 2), d0, dacc2);
+        dacc2 = mfma(read_tr_blk<kHD>(ki, lane, 1, 2), d1, dacc2);
+        dacc3 = mfma(read_tr_blk<kHD>(ki, lane, 0, 3), d0, dacc3);
+        dacc3 = mfma(read_tr_blk<kHD>(ki, lane, 1, 3), d1, dacc3);
+      }
       __builtin_amdgcn_s_setprio(0);
     }
 
     if (pref) {
-      st_pair(img(kimg, cur ^ 1), srow, scol, nk);
-      st_pair(img(vimg, cur ^ 1), srow, scol, nv);
+      st_tile<kHD>(img<kHD>(kimg, cur ^ 1), srow, scol, nk);
+      st_tile<kHD>(img<kHD>(vimg, cur ^ 1), srow, scol, nv);
     }
     __syncthreads();
     cur ^= 1;
@@ -732,8 +841,8 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
   if (kRagged && qrow >= S) return;  // stores only; no barrier follows
   __bf16* drow = dqg + (long)qrow * p.dqs.ss;
 #pragma unroll
-  for (int db = 0; db < 2; ++db) {
-    const f32x16& a = db ? dacc1 : dacc0;
+  for (int db = 0; db < kNB; ++db) {
+    const f32x16& a = db == 3 ? dacc3 : db == 2 ? dacc2 : db ? dacc1 : dacc0;
 #pragma unroll
     for (int mq = 0; mq < 4; ++mq)
       store4_bf16(drow + db * 32 + 8 * mq + 4 * hi, a[4 * mq], a[4 * mq + 1],
@@ -750,20 +859,26 @@ __global__ __launch_bounds__(256, 3) void fa_bwd_dq_kernel(FaParams p) {
 //   dV += P^T·dO   (A=packed P^T, B=dO^T tr frags)
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
-template <bool kCausal, bool kRagged, bool kDrop, bool kVarlen = false>
-__global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
+template <int kHD, bool kCausal, bool kRagged, bool kDrop,
+          bool kVarlen = false>
+__global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
+    FaParams p) {
+  static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
   static_assert(kVarlen ? kRagged : !(kCausal && kRagged),
                 "fixed-length causal needs S % 128 == 0; varlen is ragged");
+  constexpr int kNC = kHD / 16;  // 16-column chunks of a row
+  constexpr int kNB = kHD / 32;  // 32-column blocks: one accumulator each
   // 64-row q tiles, double-buffered: Q images, then dO images, then the
   // lse2/delta side tile (then the tiles' dropout q parts); the epilogue
-  // reuses [0,32K) as per-wave f32 scratch for the coalesced dV/dK stores.
+  // reuses the images as per-wave f32 scratch for the coalesced dV/dK stores.
   __shared__ __attribute__((aligned(16))) char
-      smem[4 * kImg + 1024 + kPartBytes<kDrop>];
+      smem[4 * kTileImg<kHD> + 1024 + kPartBytes<kDrop>];
   char* const qimg = smem;
-  char* const doimg = smem + 2 * kImg;
-  float* const side = reinterpret_cast<float*>(smem + 4 * kImg);
+  char* const doimg = smem + 2 * kTileImg<kHD>;
+  float* const side =
+      reinterpret_cast<float*>(smem + 4 * kTileImg<kHD>);
   [[maybe_unused]] unsigned* const qpart =
-      reinterpret_cast<unsigned*>(smem + 4 * kImg + 1024);
+      reinterpret_cast<unsigned*>(smem + 4 * kTileImg<kHD> + 1024);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -800,9 +915,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 
   // K and V^T B-fragments direct from global: lane holds
   // K[krow][chunk*16+8*hi+e] / V[krow][...]
-  bf16x8 kf[4], vf[4];
+  bf16x8 kf[kNC], vf[kNC];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
+  for (int c = 0; c < kNC; ++c) {
     kf[c] = *reinterpret_cast<const bf16x8*>(
         kg + kld * p.ks.ss + c * 16 + hi * 8);
     vf[c] = *reinterpret_cast<const bf16x8*>(
@@ -810,7 +925,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
   }
 
   const float c1 = p.scale * kLog2e;
+  // dV and dK, one accumulator per 32 columns (2, 3: head_dim 128)
   f32x16 dvacc0 = {}, dvacc1 = {}, dkacc0 = {}, dkacc1 = {};
+  [[maybe_unused]] f32x16 dvacc2 = {}, dvacc3 = {}, dkacc2 = {}, dkacc3 = {};
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
@@ -832,8 +949,10 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
     const int qb0 = t0 * 64;
     const long r0 = ld_row32<kRagged>(qb0 + srow, S);
     const long r1 = ld_row32<kRagged>(qb0 + srow + 32, S);
-    st_pair(img(qimg, 0), srow, scol, ld_pair(qg, p.qs.ss, r0, r1, scol));
-    st_pair(img(doimg, 0), srow, scol, ld_pair(dog, p.dos_.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(qimg, 0), srow, scol,
+                 ld_tile<kHD>(qg, p.qs.ss, r0, r1, scol));
+    st_tile<kHD>(img<kHD>(doimg, 0), srow, scol,
+                 ld_tile<kHD>(dog, p.dos_.ss, r0, r1, scol));
     if (threadIdx.x < 64) {
       const int rq = ld_row32<kRagged>(qb0 + (int)threadIdx.x, S);
       st_side(side, 0, threadIdx.x, ld_side(lseg, deltag, rq));
@@ -845,15 +964,15 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
 
   int cur = 0;
   for (int t = t0; t < n64; ++t) {
-    RowPair nq, nd;
+    RowTile<kHD> nq, nd;
     SideVal ns = {0.f, 0.f};
     const bool pref = t + 1 < n64;
     if (pref) {
       const int qb1 = (t + 1) * 64;
       const long r0 = ld_row32<kRagged>(qb1 + srow, S);
       const long r1 = ld_row32<kRagged>(qb1 + srow + 32, S);
-      nq = ld_pair(qg, p.qs.ss, r0, r1, scol);
-      nd = ld_pair(dog, p.dos_.ss, r0, r1, scol);
+      nq = ld_tile<kHD>(qg, p.qs.ss, r0, r1, scol);
+      nd = ld_tile<kHD>(dog, p.dos_.ss, r0, r1, scol);
       if (threadIdx.x < 64) {
         const int rq = ld_row32<kRagged>(qb1 + (int)threadIdx.x, S);
         ns = ld_side(lseg, deltag, rq);
@@ -873,17 +992,17 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
         // wave-uniform: a q half-tile or a k-row wave that is all padding
         if (qbase >= S || kbb >= S) break;
       }
-      const char* qi = img(qimg, cur) + half * kHalfImg;
-      const char* di = img(doimg, cur) + half * kHalfImg;
+      const char* qi = img<kHD>(qimg, cur) + half * kHalfImg;
+      const char* di = img<kHD>(doimg, cur) + half * kHalfImg;
       const float* lsec = side_buf(side, cur) + half * 32;
       const float* dc = lsec + kSideDelta;
 
       f32x16 sacc = {}, dp = {};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        sacc = mfma(read_row_frag(qi, lane, c), kf[c], sacc);
-        dp = mfma(read_row_frag(di, lane, c), vf[c], dp);
+      for (int c = 0; c < kNC; ++c) {
+        sacc = mfma(read_row_chunk<kHD>(qi, lane, c), kf[c], sacc);
+        dp = mfma(read_row_chunk<kHD>(di, lane, c), vf[c], dp);
       }
       __builtin_amdgcn_s_setprio(0);
 
@@ -927,59 +1046,82 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dkv_kernel(FaParams p) {
       const bf16x8 p0 = pack_frag(&pv[0]);
       const bf16x8 p1 = pack_frag(&pv[8]);
       __builtin_amdgcn_s_setprio(1);
-      dvacc0 = mfma(p0, read_tr_frag(di, lane, 0, 0), dvacc0);
-      dvacc0 = mfma(p1, read_tr_frag(di, lane, 1, 0), dvacc0);
-      dvacc1 = mfma(p0, read_tr_frag(di, lane, 0, 1), dvacc1);
-      dvacc1 = mfma(p1, read_tr_frag(di, lane, 1, 1), dvacc1);
+      dvacc0 = mfma(p0, read_tr_blk<kHD>(di, lane, 0, 0), dvacc0);
+      dvacc0 = mfma(p1, read_tr_blk<kHD>(di, lane, 1, 0), dvacc0);
+      dvacc1 = mfma(p0, read_tr_blk<kHD>(di, lane, 0, 1), dvacc1);
+      dvacc1 = mfma(p1, read_tr_blk<kHD>(di, lane, 1, 1), dvacc1);
+      if constexpr (kNB == 4) {
+        dvacc2 = mfma(p0, read_tr_blk<kHD>(di, lane, 0, 2), dvacc2);
+        dvacc2 = mfma(p1, read_tr_blk<kHD>(di, lane, 1, 2), dvacc2);
+        dvacc3 = mfma(p0, read_tr_blk<kHD>(di, lane, 0, 3), dvacc3);
+        dvacc3 = mfma(p1, read_tr_blk<kHD>(di, lane, 1, 3), dvacc3);
+      }
       __builtin_amdgcn_s_setprio(0);
       const bf16x8 e0 = pack_frag(&ds[0]);
       const bf16x8 e1 = pack_frag(&ds[8]);
       __builtin_amdgcn_s_setprio(1);
-      dkacc0 = mfma(e0, read_tr_frag(qi, lane, 0, 0), dkacc0);
-      dkacc0 = mfma(e1, read_tr_frag(qi, lane, 1, 0), dkacc0);
-      dkacc1 = mfma(e0, read_tr_frag(qi, lane, 0, 1), dkacc1);
-      dkacc1 = mfma(e1, read_tr_frag(qi, lane, 1, 1), dkacc1);
+      dkacc0 = mfma(e0, read_tr_blk<kHD>(qi, lane, 0, 0), dkacc0);
+      dkacc0 = mfma(e1, read_tr_blk<kHD>(qi, lane, 1, 0), dkacc0);
+      dkacc1 = mfma(e0, read_tr_blk<kHD>(qi, lane, 0, 1), dkacc1);
+      dkacc1 = mfma(e1, read_tr_blk<kHD>(qi, lane, 1, 1), dkacc1);
+      if constexpr (kNB == 4) {
+        dkacc2 = mfma(e0, read_tr_blk<kHD>(qi, lane, 0, 2), dkacc2);
+        dkacc2 = mfma(e1, read_tr_blk<kHD>(qi, lane, 1, 2), dkacc2);
+        dkacc3 = mfma(e0, read_tr_blk<kHD>(qi, lane, 0, 3), dkacc3);
+        dkacc3 = mfma(e1, read_tr_blk<kHD>(qi, lane, 1, 3), dkacc3);
+      }
       __builtin_amdgcn_s_setprio(0);
     }
 
     if (pref) {
-      st_pair(img(qimg, cur ^ 1), srow, scol, nq);
-      st_pair(img(doimg, cur ^ 1), srow, scol, nd);
+      st_tile<kHD>(img<kHD>(qimg, cur ^ 1), srow, scol, nq);
+      st_tile<kHD>(img<kHD>(doimg, cur ^ 1), srow, scol, nd);
       if (threadIdx.x < 64) st_side(side, cur ^ 1, threadIdx.x, ns);
     }
     __syncthreads();
     cur ^= 1;
   }
 
-  // epilogue: C[k-rows][d=lane&31] per accumulator pair -> round-trip
-  // through this wave's 8 KB LDS scratch for coalesced row-major stores.
+  // epilogue: C[k-rows][d=lane&31] per accumulator -> round-trip through
+  // this wave's [32][kHD] f32 LDS scratch (8 KB, 16 KB at head_dim 128) for
+  // coalesced row-major stores.
   __syncthreads();
-  float* scratch = reinterpret_cast<float*>(smem) + wave * 2048;  // 8 KB
+  float* scratch = reinterpret_cast<float*>(smem) + wave * (32 * kHD);
 #pragma unroll
   for (int t = 0; t < 2; ++t) {  // 0: dV, 1: dK
     const f32x16& a0 = t ? dkacc0 : dvacc0;
     const f32x16& a1 = t ? dkacc1 : dvacc1;
+    [[maybe_unused]] const f32x16& a2 = t ? dkacc2 : dvacc2;
+    [[maybe_unused]] const f32x16& a3 = t ? dkacc3 : dvacc3;
     if (kDrop && t == 0) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        scratch[crow(r, hi) * 64 + (lane & 31)] = a0[r] * p.drop_rp;
-        scratch[crow(r, hi) * 64 + 32 + (lane & 31)] = a1[r] * p.drop_rp;
+        scratch[crow(r, hi) * kHD + (lane & 31)] = a0[r] * p.drop_rp;
+        scratch[crow(r, hi) * kHD + 32 + (lane & 31)] = a1[r] * p.drop_rp;
+        if constexpr (kNB == 4) {
+          scratch[crow(r, hi) * kHD + 64 + (lane & 31)] = a2[r] * p.drop_rp;
+          scratch[crow(r, hi) * kHD + 96 + (lane & 31)] = a3[r] * p.drop_rp;
+        }
       }
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        scratch[crow(r, hi) * 64 + (lane & 31)] = a0[r];
-        scratch[crow(r, hi) * 64 + 32 + (lane & 31)] = a1[r];
+        scratch[crow(r, hi) * kHD + (lane & 31)] = a0[r];
+        scratch[crow(r, hi) * kHD + 32 + (lane & 31)] = a1[r];
+        if constexpr (kNB == 4) {
+          scratch[crow(r, hi) * kHD + 64 + (lane & 31)] = a2[r];
+          scratch[crow(r, hi) * kHD + 96 + (lane & 31)] = a3[r];
+        }
       }
     }
     __builtin_amdgcn_s_waitcnt(0);  // drain LDS writes (wave-local reuse)
     __bf16* outg = (t ? dkg : dvg);
     const TStride& os = t ? p.dks : p.dvs;
     const int row = lane >> 1;           // 2 lanes per k row
-    const int dhalf = (lane & 1) * 32;
+    const int dhalf = (lane & 1) * (kHD / 2);
 #pragma unroll
-    for (int mq = 0; mq < 8; ++mq) {
-      const float* src = scratch + row * 64 + dhalf + mq * 4;
+    for (int mq = 0; mq < kHD / 8; ++mq) {
+      const float* src = scratch + row * kHD + dhalf + mq * 4;
       if (!kRagged || kbb + row < S)
         store4_bf16(outg + (long)(kbb + row) * os.ss + dhalf + mq * 4, src[0],
                     src[1], src[2], src[3]);
@@ -1191,25 +1333,44 @@ void set_varlen(FaParams& p, const int* tmap, int total) {
   p.total = total;
 }
 
-void launch_fwd(const FaParams& p, dim3 grid, bool causal, bool drop,
-                bool varlen, hipStream_t stream) {
-  with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                   kD = decltype(d)::value, kV = decltype(vl)::value;
-    hipLaunchKernelGGL((fa_fwd_kernel<kC, kR, kD, kV>), grid, dim3(256), 0,
-                       stream, p);
+// Calls f(kHD) with the head dimension as a std::integral_constant.
+template <typename F>
+void with_head_dim(const char* name, int head_dim, F&& f) {
+  if (head_dim == 64)
+    f(std::integral_constant<int, 64>{});
+  else if (head_dim == 128)
+    f(std::integral_constant<int, 128>{});
+  else
+    throw std::runtime_error(std::string(name) +
+                             ": head_dim must be 64 or 128, got " +
+                             std::to_string(head_dim));
+}
+
+void launch_fwd(const FaParams& p, dim3 grid, int head_dim, bool causal,
+                bool drop, bool varlen, hipStream_t stream) {
+  with_head_dim("fa_forward", head_dim, [&](auto hd) {
+    with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
+      constexpr int kHD = decltype(hd)::value;
+      constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                     kD = decltype(d)::value, kV = decltype(vl)::value;
+      hipLaunchKernelGGL((fa_fwd_kernel<kHD, kC, kR, kD, kV>), grid,
+                         dim3(256), 0, stream, p);
+    });
   });
 }
 
-void launch_bwd(const FaParams& p, dim3 grid, bool causal, bool drop,
-                bool varlen, hipStream_t stream) {
-  with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
-    constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                   kD = decltype(d)::value, kV = decltype(vl)::value;
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<kC, kR, kD, kV>), grid, dim3(256),
-                       0, stream, p);
-    hipLaunchKernelGGL((fa_bwd_dkv_kernel<kC, kR, kD, kV>), grid, dim3(256),
-                       0, stream, p);
+void launch_bwd(const FaParams& p, dim3 grid, int head_dim, bool causal,
+                bool drop, bool varlen, hipStream_t stream) {
+  with_head_dim("fa_backward", head_dim, [&](auto hd) {
+    with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
+      constexpr int kHD = decltype(hd)::value;
+      constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                     kD = decltype(d)::value, kV = decltype(vl)::value;
+      hipLaunchKernelGGL((fa_bwd_dq_kernel<kHD, kC, kR, kD, kV>), grid,
+                         dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((fa_bwd_dkv_kernel<kHD, kC, kR, kD, kV>), grid,
+                         dim3(256), 0, stream, p);
+    });
   });
 }
 
@@ -1219,7 +1380,8 @@ void launch_bwd(const FaParams& p, dim3 grid, bool causal, bool drop,
 unsigned fa_drop_threshold(double p) { return drop_threshold(p); }
 
 // ---------------------------------------------------------------------------
-// Host launchers (bound in bindings.hip). dropout_p == 0 launches the
+// Host launchers (bound in bindings.hip). head_dim, the width of a q, k, v,
+// o row, is 64 or 128; anything else throws. dropout_p == 0 launches the
 // kDrop=false instantiations, which are the kernels without dropout, and
 // never touches seed; dropout_p > 0 reads the 64-bit seed at `seed` (device
 // memory) when the kernel runs.
@@ -1227,13 +1389,13 @@ unsigned fa_drop_threshold(double p) { return drop_threshold(p); }
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
-                double dropout_p, const long* seed) {
+                double dropout_p, const long* seed, int head_dim) {
   check_len("fa_forward", S, causal);
   check_drop("fa_forward", dropout_p, seed);
   FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
   set_drop(p, dropout_p, seed);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  launch_fwd(p, grid, causal, dropout_p > 0.0, false, stream);
+  launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, false, stream);
 }
 
 // strides: q, k, v, o, dO, dq, dk, dv. delta is a [B,H,S] f32 workspace the
@@ -1242,7 +1404,7 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
-                 double dropout_p, const long* seed) {
+                 double dropout_p, const long* seed, int head_dim) {
   check_len("fa_backward", S, causal);
   check_drop("fa_backward", dropout_p, seed);
   FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
@@ -1250,12 +1412,12 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
   set_drop(p, dropout_p, seed);
   bwd_params(p, do_, delta, dq, dk, dv, strides);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
-  launch_bwd(p, grid, causal, dropout_p > 0.0, false, stream);
+  launch_bwd(p, grid, head_dim, causal, dropout_p > 0.0, false, stream);
 }
 
 // ---------------------------------------------------------------------------
-// Variable-length launchers. Tensors are [total, H, 64] views (strides as
-// above with the batch stride unused), lse and delta fp32 [H, total], tmap
+// Variable-length launchers. Tensors are [total, H, head_dim] views (strides
+// as above with the batch stride unused), lse and delta fp32 [H, total], tmap
 // the int32 [total/128 + n_seqs, 4] map that fa_varlen_plan filled on the
 // same stream. Nothing here reads cu_seqlens or the map on the host.
 // ---------------------------------------------------------------------------
@@ -1274,14 +1436,14 @@ void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
                        float* lse, const int* tmap, int total, int n_seqs,
                        int H, const long* strides, float scale,
                        hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed) {
+                       const long* seed, int head_dim) {
   check_varlen("fa_varlen_forward", total, n_seqs, H);
   check_drop("fa_varlen_forward", dropout_p, seed);
   FaParams p = fwd_params(q, k, v, o, lse, H, 0, strides, scale);
   set_drop(p, dropout_p, seed);
   set_varlen(p, tmap, total);
   const dim3 grid(varlen_max_tiles(total, n_seqs), H);
-  launch_fwd(p, grid, causal, dropout_p > 0.0, true, stream);
+  launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, true, stream);
 }
 
 void fa_varlen_backward(const void* q, const void* k, const void* v,
@@ -1289,7 +1451,8 @@ void fa_varlen_backward(const void* q, const void* k, const void* v,
                         float* delta, void* dq, void* dk, void* dv,
                         const int* tmap, int total, int n_seqs, int H,
                         const long* strides, float scale, hipStream_t stream,
-                        bool causal, double dropout_p, const long* seed) {
+                        bool causal, double dropout_p, const long* seed,
+                        int head_dim) {
   check_varlen("fa_varlen_backward", total, n_seqs, H);
   check_drop("fa_varlen_backward", dropout_p, seed);
   FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
@@ -1298,7 +1461,7 @@ void fa_varlen_backward(const void* q, const void* k, const void* v,
   set_varlen(p, tmap, total);
   bwd_params(p, do_, delta, dq, dk, dv, strides);
   const dim3 grid(varlen_max_tiles(total, n_seqs), H);
-  launch_bwd(p, grid, causal, dropout_p > 0.0, true, stream);
+  launch_bwd(p, grid, head_dim, causal, dropout_p > 0.0, true, stream);
 }
 
 // out: [B,H,S,S] bytes, 1 where the element is kept.

@@ -101,12 +101,12 @@ void ce_backward(int dtype, const void* logits, const void* targets,
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
-                double dropout_p, const long* seed);
+                double dropout_p, const long* seed, int head_dim);
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
-                 double dropout_p, const long* seed);
+                 double dropout_p, const long* seed, int head_dim);
 void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
                      double dropout_p, hipStream_t stream);
 void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
@@ -115,13 +115,14 @@ void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
                        float* lse, const int* tmap, int total, int n_seqs,
                        int H, const long* strides, float scale,
                        hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed);
+                       const long* seed, int head_dim);
 void fa_varlen_backward(const void* q, const void* k, const void* v,
                         const void* o, const void* do_, const float* lse,
                         float* delta, void* dq, void* dk, void* dv,
                         const int* tmap, int total, int n_seqs, int H,
                         const long* strides, float scale, hipStream_t stream,
-                        bool causal, double dropout_p, const long* seed);
+                        bool causal, double dropout_p, const long* seed,
+                        int head_dim);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -282,29 +283,31 @@ PYBIND11_MODULE(_core, m) {
   m.def("fa_fwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            int B, int H, int S, const std::vector<long>& strides, float scale,
-           uintptr_t stream, bool causal, double dropout_p, uintptr_t seed) {
+           uintptr_t stream, bool causal, double dropout_p, uintptr_t seed,
+           int head_dim) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_fwd: need 12 strides");
           adapcc::fa_forward((const void*)q, (const void*)k, (const void*)v,
                              (void*)o, (float*)lse, B, H, S, strides.data(),
                              scale, reinterpret_cast<hipStream_t>(stream),
-                             causal, dropout_p, (const long*)seed);
+                             causal, dropout_p, (const long*)seed, head_dim);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
         // causal=False: non-causal self-attention, any S >= 1.
         // dropout_p > 0: seed is the address of one int64 in device memory
+        // head_dim: 64 or 128, the width of a q/k/v/o row
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("S"),
         py::arg("strides"), py::arg("scale"), py::arg("stream"),
         py::arg("causal") = true, py::arg("dropout_p") = 0.0,
-        py::arg("seed") = 0);
+        py::arg("seed") = 0, py::arg("head_dim") = 64);
   m.def("fa_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, int B, int H, int S, const std::vector<long>& strides,
            float scale, uintptr_t stream, bool causal, double dropout_p,
-           uintptr_t seed) {
+           uintptr_t seed, int head_dim) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_bwd: need 24 strides");
           adapcc::fa_backward((const void*)q, (const void*)k, (const void*)v,
@@ -312,7 +315,7 @@ PYBIND11_MODULE(_core, m) {
                               (const float*)lse, (float*)delta, (void*)dq,
                               (void*)dk, (void*)dv, B, H, S, strides.data(),
                               scale, reinterpret_cast<hipStream_t>(stream),
-                              causal, dropout_p, (const long*)seed);
+                              causal, dropout_p, (const long*)seed, head_dim);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -321,7 +324,8 @@ PYBIND11_MODULE(_core, m) {
         py::arg("dk"), py::arg("dv"), py::arg("B"), py::arg("H"),
         py::arg("S"), py::arg("strides"), py::arg("scale"),
         py::arg("stream"), py::arg("causal") = true,
-        py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
+        py::arg("head_dim") = 64);
   // out: [B,H,S,S] uint8, 1 where the attention kernels keep the element
   m.def("fa_dropout_mask",
         [](uintptr_t out, uintptr_t seed, int B, int H, int S,
@@ -348,20 +352,20 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("cu_seqlens"), py::arg("n_seqs"), py::arg("total"),
         py::arg("tmap"), py::arg("stream"));
-  // q, k, v, o: [total, H, 64] views, strides as in fa_fwd (batch stride
+  // q, k, v, o: [total, H, head_dim] views, strides as in fa_fwd (batch stride
   // unused); lse: fp32 [H, total]
   m.def("fa_varlen_fwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            uintptr_t tmap, int total, int n_seqs, int H,
            const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed) {
+           bool causal, double dropout_p, uintptr_t seed, int head_dim) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_varlen_fwd: need 12 strides");
           adapcc::fa_varlen_forward(
               (const void*)q, (const void*)k, (const void*)v, (void*)o,
               (float*)lse, (const int*)tmap, total, n_seqs, H, strides.data(),
               scale, reinterpret_cast<hipStream_t>(stream), causal, dropout_p,
-              (const long*)seed);
+              (const long*)seed, head_dim);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -369,13 +373,13 @@ PYBIND11_MODULE(_core, m) {
         py::arg("lse"), py::arg("tmap"), py::arg("total"), py::arg("n_seqs"),
         py::arg("H"), py::arg("strides"), py::arg("scale"), py::arg("stream"),
         py::arg("causal") = true, py::arg("dropout_p") = 0.0,
-        py::arg("seed") = 0);
+        py::arg("seed") = 0, py::arg("head_dim") = 64);
   m.def("fa_varlen_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, uintptr_t tmap, int total, int n_seqs, int H,
            const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed) {
+           bool causal, double dropout_p, uintptr_t seed, int head_dim) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_varlen_bwd: need 24 strides");
           adapcc::fa_varlen_backward(
@@ -383,7 +387,7 @@ PYBIND11_MODULE(_core, m) {
               (const void*)dout, (const float*)lse, (float*)delta, (void*)dq,
               (void*)dk, (void*)dv, (const int*)tmap, total, n_seqs, H,
               strides.data(), scale, reinterpret_cast<hipStream_t>(stream),
-              causal, dropout_p, (const long*)seed);
+              causal, dropout_p, (const long*)seed, head_dim);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -392,7 +396,8 @@ PYBIND11_MODULE(_core, m) {
         py::arg("dk"), py::arg("dv"), py::arg("tmap"), py::arg("total"),
         py::arg("n_seqs"), py::arg("H"), py::arg("strides"),
         py::arg("scale"), py::arg("stream"), py::arg("causal") = true,
-        py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
+        py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
+        py::arg("head_dim") = 64);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

@@ -1,17 +1,20 @@
 """Flash-attention kernel timing: hand-written CDNA4 kernels vs torch SDPA.
 
-Run on a GPU box:  python benchmarks/attn_bench.py [--shape gpt2|vit|varlen]
-                                                   [--dropout P]
+Run on a GPU box:  python benchmarks/attn_bench.py
+                       [--shape gpt2|vit|gpt2-d128|vit-d128|varlen]
+                       [--dropout P] [--head-dim 64|128]
 
 gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
-(ViT-base at 224 px). --dropout P times both paths with attention dropout at
+(ViT-base at 224 px). gpt2-d128: B32 H16 S1024 D128, causal; vit-d128: B64 H8
+S197 D128, non-causal: the head_dim 128 kernels. --dropout P times both paths with attention dropout at
 rate P (ours inside the kernels, a fresh seed drawn per call as in training).
 varlen: 131072 tokens of H12 D64 causal packed sequences through
 flash_attention_qkv_varlen, first as 128 sequences of 1024 against the
 fixed-length packed kernel on the same work (the cost of the mode), then as
 a seeded mix of lengths drawn log-uniformly in [16, 1024] against the same
 documents padded to 1024 and against SDPA under a dense block-diagonal mask
-(what the mode is for), and the plan kernel by itself.
+(what the mode is for), and the plan kernel by itself. --head-dim 128 (varlen
+only) runs the same token count as H6 D128.
 """
 import argparse
 import math
@@ -27,6 +30,8 @@ SHAPES = {
     # name: (B, H, S, D, causal)
     "gpt2": (64, 12, 1024, 64, True),
     "vit": (64, 12, 197, 64, False),
+    "gpt2-d128": (32, 16, 1024, 128, True),
+    "vit-d128": (64, 8, 197, 128, False),
 }
 
 
@@ -52,12 +57,15 @@ def main():
                          "whose calls are ~10x shorter)")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="attention dropout rate for both paths")
+    ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64,
+                    help="varlen only: 128 halves the heads, same tokens")
     args = ap.parse_args()
     drop = args.dropout
     if args.shape == "varlen":
-        return varlen_path(args.iters or 20, drop)
+        return varlen_path(args.iters or 20, drop,
+                           H=12 * 64 // args.head_dim, D=args.head_dim)
     B, H, S, D, causal = SHAPES[args.shape]
-    iters = args.iters or (200 if args.shape == "vit" else 20)
+    iters = args.iters or (200 if args.shape.startswith("vit") else 20)
 
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)

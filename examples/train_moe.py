@@ -10,6 +10,8 @@ hook).
 ``--top-k 2`` routes every token to its two best experts; a non-zero
 ``--aux-coef`` adds that multiple of the layer's load-balancing loss to the
 training loss (0.01 is the usual Switch/GShard value).
+``--fused-attention`` computes the block's attention with
+``flash_attention_qkv`` on the same ``nn.MultiheadAttention`` weights.
 """
 
 from __future__ import annotations
@@ -39,6 +41,9 @@ def main():
     p.add_argument("--top-k", type=int, default=1, choices=(1, 2))
     p.add_argument("--aux-coef", type=float, default=0.0,
                    help="weight of the load-balancing loss (0 = off)")
+    p.add_argument("--fused-attention", action="store_true",
+                   help="attention through flash_attention_qkv (the CDNA4 "
+                        "kernels in bf16 at head_dim 64 or 128)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -61,6 +66,7 @@ def main():
         d_model=args.d_model, n_head=8, d_hidden=args.d_hidden,
         num_local_experts=args.local_experts, comm=comm, world_size=world,
         rank=rank, top_k=args.top_k, balance_loss=args.aux_coef != 0.0,
+        fused_attention=args.fused_attention,
     ).to(device)
     # expert weights are rank-local (expert parallel): re-init per rank
     torch.manual_seed(100 + rank)
