@@ -31,6 +31,10 @@ class GPT2Config:
     # dropout on each sublayer's output before it joins the residual stream
     # (transformers' resid_pdrop), fused with the add and the next LayerNorm
     resid_dropout: float = 0.0
+    # K/V heads (grouped-query attention; 1: multi-query). None: n_head.
+    # Must divide n_head; query head h reads K/V head h // (n_head //
+    # n_kv_head), and c_attn is (n_head + 2*n_kv_head) * head_dim wide
+    n_kv_head: int = None
 
     @classmethod
     def small(cls) -> "GPT2Config":
@@ -51,7 +55,12 @@ class CausalSelfAttention(nn.Module):
         super().__init__()
         assert cfg.n_embd % cfg.n_head == 0
         self.n_head = cfg.n_head
-        self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
+        self.n_kv_head = (cfg.n_head if cfg.n_kv_head is None
+                          else cfg.n_kv_head)
+        assert self.n_kv_head >= 1 and cfg.n_head % self.n_kv_head == 0
+        head_dim = cfg.n_embd // cfg.n_head
+        self.c_attn = nn.Linear(
+            cfg.n_embd, (cfg.n_head + 2 * self.n_kv_head) * head_dim)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
         self.dropout = cfg.dropout
 
@@ -66,12 +75,13 @@ class CausalSelfAttention(nn.Module):
             qkv = self.c_attn(x)
             y = attention.flash_attention_qkv_varlen(
                 qkv.view(qkv.shape[1], qkv.shape[2]), self.n_head,
-                cu_seqlens, dropout_p=p)
+                cu_seqlens, dropout_p=p, n_kv_head=self.n_kv_head)
             return self.c_proj(y.view(1, y.shape[0], y.shape[1]))
         # packed [B,T,3C] in, [B,T,C] out: no split/transpose copies
         return self.c_proj(attention.flash_attention_qkv(
             self.c_attn(x), self.n_head,
             dropout_p=self.dropout if self.training else 0.0,
+            n_kv_head=self.n_kv_head,
         ))
 
 

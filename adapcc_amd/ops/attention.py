@@ -1,17 +1,24 @@
 """Hand-written CDNA4 flash attention (csrc/attn.hip) with autograd.
 
 Supported fast paths, both bf16, head_dim 64 or 128, self-attention (q, k, v
-of one shape), attention dropout 0 <= p < 1: causal with seq len a multiple
+of one length), attention dropout 0 <= p < 1: causal with seq len a multiple
 of 128 (GPT-2), and non-causal with any seq len >= 1 (ViT: 197). Anything else
-falls back to torch SDPA. Tensors are [B, H, S, D] with any batch/head/row
-strides (rows must be contiguous and 16-B aligned), so the usual
+falls back to torch SDPA. k and v may have fewer heads than q (grouped-query
+attention, multi-query with one): q is [B,H,S,D], k and v [B,Hk,S,D] with
+H % Hk == 0, and query head h reads K/V head h // (H // Hk). The kernels
+index K/V that way themselves, and the backward sums dk and dv over each
+group in its fp32 accumulators, so nothing is expanded or reduced outside
+them and dk, dv have k's shape. Tensors are [B, H, S, D] with any
+batch/head/row strides (rows must be contiguous and 16-B aligned), so the usual
 ``.view(B,T,H,hd).transpose(1,2)`` projection views work without a copy.
 ``flash_attention_qkv`` takes the packed [B,T,3C] projection and returns
-[B,T,C], reading and writing both layouts in place, in either mode.
+[B,T,C], reading and writing both layouts in place, in either mode; with
+``n_kv_head`` the projection is [B,T,(H + 2*Hk)*D], q columns, then k, then v.
 
 Dropout acts on the attention probabilities inside the kernels. The mask is
 a pure function keep(seed, b*H+h, q, k) (csrc/attn_drop.h) that the backward
-regenerates, never a stored tensor; kept probabilities are multiplied by
+regenerates, never a stored tensor (H and h are the query heads, also with
+fewer K/V heads); kept probabilities are multiplied by
 1/(1-p). The 64-bit seed is one int64 on the device, read when the kernels
 run: drawn from torch's generator per call (so ``torch.manual_seed``
 reproduces a run, without a host sync, and a captured graph that refills it
@@ -78,9 +85,23 @@ def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
     return bool(_core())
 
 
+def _gqa_shapes_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                   heads_at: int) -> bool:
+    """k and v of one shape that is q's in every dimension but the heads'
+    (``heads_at``), where their size divides q's."""
+    if q.dim() != k.dim() or k.shape != v.shape:
+        return False
+    H, Hk = q.shape[heads_at], k.shape[heads_at]
+    if Hk < 1 or H % Hk != 0:
+        return False
+    return all(a == b for i, (a, b) in enumerate(zip(q.shape, k.shape))
+               if i != heads_at)
+
+
 def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                  causal: bool, dropout_p: float) -> bool:
-    if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
+    """q [B,H,S,D]; k, v [B,Hk,S,D] of one shape with H % Hk == 0."""
+    if q.dim() != 4 or not _gqa_shapes_ok(q, k, v, 1):
         return False
     if not (_row_ok(q) and _row_ok(k) and _row_ok(v)):
         return False
@@ -170,7 +191,7 @@ def _launch_fwd(q, k, v, o, lse, scale, causal=True, dropout_p=0.0,
     _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    lse.data_ptr(), B, H, S, strides, scale, stream, causal,
                    dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0,
-                   head_dim=q.shape[3])
+                   head_dim=q.shape[3], n_kv_head=k.shape[1])
 
 
 def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
@@ -178,7 +199,8 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
     """dq/dk/dv are written in place; delta = rowsum(dO*O) is computed by
     the dq kernel into a workspace (``delta``: contiguous [B,H,S] fp32, made
     here when not given) the dkv kernel then reads. With dropout, ``seed``
-    is the forward's seed tensor."""
+    is the forward's seed tensor. k, v, dk, dv may have fewer heads than q
+    (H % Hk == 0); dk, dv are then the sums over each group."""
     B, H, S, _ = q.shape
     # e.g. y.sum().backward() hands down an expanded, zero-stride dout
     do = dout if _row_ok(dout) else dout.contiguous()
@@ -193,7 +215,7 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
                    strides, scale, stream, causal, dropout_p,
                    seed.data_ptr() if dropout_p > 0.0 else 0,
-                   head_dim=q.shape[3])
+                   head_dim=q.shape[3], n_kv_head=k.shape[1])
 
 
 def _fa_forward_lse(q, k, v, scale, causal, dropout_p=0.0, seed=None):
@@ -214,6 +236,29 @@ def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
     """[B,T,C] (any row stride) -> its [B,H,T,C/H] view."""
     B, T, C = t.shape
     return t.view(B, T, n_head, C // n_head).transpose(1, 2)
+
+
+def _kv_heads(name: str, n_head: int, n_kv_head: Optional[int]) -> int:
+    """The K/V head count of a packed projection: n_head when not given."""
+    Hk = n_head if n_kv_head is None else int(n_kv_head)
+    if n_head < 1 or Hk < 1 or n_head % Hk != 0:
+        raise ValueError(f"{name}: n_kv_head must divide n_head, got "
+                         f"n_head {n_head}, n_kv_head {n_kv_head}")
+    return Hk
+
+
+def _qkv_parts(t: torch.Tensor, n_head: int, Hk: int):
+    """The q, k, v column ranges of a packed [.., (H + 2*Hk)*D] tensor:
+    H*D q columns, then Hk*D of k, then Hk*D of v (thirds when Hk == H)."""
+    D = t.shape[-1] // (n_head + 2 * Hk)
+    return t.split([n_head * D, Hk * D, Hk * D], dim=-1)
+
+
+def _qkv_heads(t: torch.Tensor, n_head: int, Hk: int, heads=None):
+    """The three parts of t as [B,H,T,D], [B,Hk,T,D], [B,Hk,T,D] views."""
+    heads = heads or _heads
+    q, k, v = _qkv_parts(t, n_head, Hk)
+    return heads(q, n_head), heads(k, Hk), heads(v, Hk)
 
 
 def _drop_kw(ctx, seed):
@@ -243,8 +288,8 @@ class _FlashAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, o, lse, *seed = ctx.saved_tensors
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
+        dk = torch.empty(k.shape, dtype=q.dtype, device=q.device)
+        dv = torch.empty_like(dk)
         _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale,
                     causal=ctx.causal,
                     **_drop_kw(ctx, seed[0] if seed else None))
@@ -253,19 +298,22 @@ class _FlashAttnFn(torch.autograd.Function):
 
 class _FlashAttnQkvFn(torch.autograd.Function):
     """Attention straight off the packed projection: q, k, v are strided
-    views of qkv [B,T,3C], O is written as [B,T,C], and the backward writes
-    dq, dk, dv into the three thirds of one [B,T,3C] gradient."""
+    views of qkv [B,T,(H+2*Hk)*D] (n_kv_head None: Hk = H, [B,T,3C]), O is
+    written as [B,T,H*D], and the backward writes dq, dk, dv into the three
+    parts of one gradient of qkv's shape."""
 
     @staticmethod
-    def forward(ctx, qkv, n_head, scale, causal, dropout_p=0.0, seed=None):
+    def forward(ctx, qkv, n_head, scale, causal, dropout_p=0.0, seed=None,
+                n_kv_head=None):
         B, T, C3 = qkv.shape
-        C = C3 // 3
-        q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+        Hk = n_head if n_kv_head is None else n_kv_head
+        C = C3 // (n_head + 2 * Hk) * n_head
+        q, k, v = _qkv_heads(qkv, n_head, Hk)
         y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((B, n_head, T), dtype=torch.float32,
                           device=qkv.device)
         ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
-        ctx.dropout_p = dropout_p
+        ctx.dropout_p, ctx.n_kv_head = dropout_p, Hk
         _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal,
                     **_drop_kw(ctx, seed))
         if dropout_p > 0.0:
@@ -278,14 +326,13 @@ class _FlashAttnQkvFn(torch.autograd.Function):
     def backward(ctx, dy):
         qkv, y, lse, *seed = ctx.saved_tensors
         H = ctx.n_head
-        C = y.shape[2]
-        q, k, v = (_heads(t, H) for t in qkv.split(C, dim=2))
+        q, k, v = _qkv_heads(qkv, H, ctx.n_kv_head)
         dqkv = torch.empty_like(qkv)
-        dq, dk, dv = (_heads(t, H) for t in dqkv.split(C, dim=2))
+        dq, dk, dv = _qkv_heads(dqkv, H, ctx.n_kv_head)
         _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
                     ctx.scale, causal=ctx.causal,
                     **_drop_kw(ctx, seed[0] if seed else None))
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -294,7 +341,10 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     dropout_seed: Optional[torch.Tensor] = None
                     ) -> torch.Tensor:
     """SDPA drop-in for [B,H,S,D] inputs; runs the hand-written CDNA4
-    kernels when the shape qualifies, torch SDPA otherwise. dropout_seed
+    kernels when the shape qualifies, torch SDPA otherwise. k and v may be
+    [B,Hk,S,D] with H % Hk == 0 (grouped-query attention): query head h
+    reads K/V head h // (H // Hk), and dk, dv come back in k's shape.
+    dropout_seed
     (kernels only): one-element int64 tensor on the device that fixes the
     dropout mask; drawn from torch's generator when absent."""
     if fa_supported(q, k, v, causal, dropout_p):
@@ -302,6 +352,18 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         seed = (_seed_tensor(dropout_seed, q.device) if dropout_p > 0.0
                 else None)
         return _FlashAttnFn.apply(q, k, v, s, causal, dropout_p, seed)
+    if q.dim() == 4 and k.dim() == 4 and v.dim() == 4:
+        H, Hk = q.shape[1], k.shape[1]
+        if v.shape[1] != Hk:
+            raise ValueError("flash_attention: k and v must have one head "
+                             f"count, got {Hk} and {v.shape[1]}")
+        if Hk != H:
+            if Hk < 1 or H % Hk != 0:
+                raise ValueError("flash_attention: the K/V head count must "
+                                 f"divide q's, got {H} and {Hk}")
+            return torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale,
+                enable_gqa=True)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
 
@@ -309,46 +371,63 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
                             dropout_p: float = 0.0,
                             causal: bool = True,
-                            dropout_seed: Optional[torch.Tensor] = None
+                            dropout_seed: Optional[torch.Tensor] = None,
+                            n_kv_head: Optional[int] = None
                             ) -> torch.Tensor:
     """split -> head views -> flash_attention -> [B,T,C]."""
     B, T, C3 = qkv.shape
-    C = C3 // 3
-    q, k, v = (_heads(t, n_head) for t in qkv.split(C, dim=2))
+    Hk = _kv_heads("flash_attention_qkv", n_head, n_kv_head)
+    q, k, v = _qkv_heads(qkv, n_head, Hk)
     y = flash_attention(q, k, v, causal=causal, dropout_p=dropout_p,
                         dropout_seed=dropout_seed)
-    return y.transpose(1, 2).contiguous().view(B, T, C)
+    return y.transpose(1, 2).contiguous().view(B, T, n_head * q.shape[3])
+
+
+def _qkv_width(n_head: int, n_kv_head: Optional[int]) -> int:
+    """Heads across a packed projection's row, H + 2*Hk; 0 when n_kv_head
+    does not divide n_head."""
+    Hk = n_head if n_kv_head is None else n_kv_head
+    if n_head < 1 or Hk < 1 or n_head % Hk != 0:
+        return 0
+    return n_head + 2 * Hk
 
 
 def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
-                     dropout_p: float, causal: bool = True) -> bool:
-    if qkv.dim() != 3 or qkv.shape[0] < 1 or qkv.shape[2] % (3 * n_head):
+                     dropout_p: float, causal: bool = True,
+                     n_kv_head: Optional[int] = None) -> bool:
+    W = _qkv_width(n_head, n_kv_head)
+    if not W or qkv.dim() != 3 or qkv.shape[0] < 1 or qkv.shape[2] % W:
         return False
     if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
         return False
-    return _kernel_ok(qkv, qkv.shape[2] // (3 * n_head), qkv.shape[1],
-                      causal, dropout_p)
+    return _kernel_ok(qkv, qkv.shape[2] // W, qkv.shape[1], causal,
+                      dropout_p)
 
 
 def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
                         dropout_p: float = 0.0,
                         causal: bool = True,
-                        dropout_seed: Optional[torch.Tensor] = None
+                        dropout_seed: Optional[torch.Tensor] = None,
+                        n_kv_head: Optional[int] = None
                         ) -> torch.Tensor:
     """Self-attention on the packed projection qkv [B,T,3C] (q, k, v
-    thirds, heads contiguous within each); returns [B,T,C]. The qualifying
+    thirds, heads contiguous within each); returns [B,T,C]. With n_kv_head
+    = Hk < n_head (it must divide n_head) the projection is
+    [B,T,(H + 2*Hk)*D]: H*D q columns, then Hk*D of k, then Hk*D of v, and
+    the result [B,T,H*D]. The qualifying
     case (bf16, head_dim 64 or 128, contiguous, dropout_p < 1; T a multiple
     of 128 when causal, any T >= 1 when not) runs the CDNA4 kernels directly
     on the packed layout with no copies; anything else composes
     ``flash_attention`` from views. dropout_seed as in ``flash_attention``."""
-    if fa_qkv_supported(qkv, n_head, dropout_p, causal):
-        scale = 1.0 / math.sqrt(qkv.shape[2] // (3 * n_head))
+    Hk = _kv_heads("flash_attention_qkv", n_head, n_kv_head)
+    if fa_qkv_supported(qkv, n_head, dropout_p, causal, Hk):
+        scale = 1.0 / math.sqrt(qkv.shape[2] // (n_head + 2 * Hk))
         seed = (_seed_tensor(dropout_seed, qkv.device) if dropout_p > 0.0
                 else None)
         return _FlashAttnQkvFn.apply(qkv, n_head, scale, causal, dropout_p,
-                                     seed)
+                                     seed, Hk)
     return _attention_qkv_composed(qkv, n_head, dropout_p, causal,
-                                   dropout_seed)
+                                   dropout_seed, Hk)
 
 
 # ---------------------------------------------------------------------------
@@ -396,7 +475,8 @@ def _varlen_kernel_ok(t: torch.Tensor, D: int, total: int,
 def fa_varlen_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                         cu_seqlens: torch.Tensor, causal: bool,
                         dropout_p: float) -> bool:
-    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+    """q [total,H,D]; k, v [total,Hk,D] of one shape with H % Hk == 0."""
+    if q.dim() != 3 or not _gqa_shapes_ok(q, k, v, 1):
         return False
     if not _cu_ok(cu_seqlens, q.device):
         return False
@@ -407,15 +487,17 @@ def fa_varlen_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 def fa_qkv_varlen_supported(qkv: torch.Tensor, n_head: int,
                             cu_seqlens: torch.Tensor, dropout_p: float,
-                            causal: bool = True) -> bool:
-    if qkv.dim() != 2 or qkv.shape[1] % (3 * n_head):
+                            causal: bool = True,
+                            n_kv_head: Optional[int] = None) -> bool:
+    W = _qkv_width(n_head, n_kv_head)
+    if not W or qkv.dim() != 2 or qkv.shape[1] % W:
         return False
     if not _cu_ok(cu_seqlens, qkv.device):
         return False
     if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
         return False
-    return _varlen_kernel_ok(qkv, qkv.shape[1] // (3 * n_head),
-                             qkv.shape[0], dropout_p)
+    return _varlen_kernel_ok(qkv, qkv.shape[1] // W, qkv.shape[0],
+                             dropout_p)
 
 
 def varlen_tile_map_reference(cu_seqlens, total: int) -> torch.Tensor:
@@ -474,7 +556,7 @@ def _launch_varlen_fwd(q, k, v, o, lse, tmap, n_seqs, scale, causal=True,
                           total, n_seqs, H, strides, scale, stream, causal,
                           dropout_p,
                           seed.data_ptr() if dropout_p > 0.0 else 0,
-                          head_dim=q.shape[3])
+                          head_dim=q.shape[3], n_kv_head=k.shape[1])
 
 
 def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
@@ -497,7 +579,7 @@ def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
                           dv.data_ptr(), tmap.data_ptr(), total, n_seqs, H,
                           strides, scale, stream, causal, dropout_p,
                           seed.data_ptr() if dropout_p > 0.0 else 0,
-                          head_dim=q.shape[3])
+                          head_dim=q.shape[3], n_kv_head=k.shape[1])
 
 
 def _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale, causal,
@@ -533,8 +615,8 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, o, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
+        dk = torch.empty(k.shape, dtype=q.dtype, device=q.device)
+        dv = torch.empty_like(dk)
         _launch_varlen_bwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o),
                            _rows4(dout), lse, _rows4(dq), _rows4(dk),
                            _rows4(dv), tmap, cu_seqlens.numel() - 1,
@@ -550,21 +632,22 @@ def _heads2(t: torch.Tensor, n_head: int) -> torch.Tensor:
 
 class _FlashAttnQkvVarlenFn(torch.autograd.Function):
     """_FlashAttnQkvFn for packed sequences: q, k, v are strided views of
-    qkv [total,3C], O is written as [total,C], and the backward writes dq,
-    dk, dv into the three thirds of one [total,3C] gradient."""
+    qkv [total,(H+2*Hk)*D], O is written as [total,H*D], and the backward
+    writes dq, dk, dv into the three parts of one gradient of qkv's shape."""
 
     @staticmethod
     def forward(ctx, qkv, n_head, cu_seqlens, scale, causal, dropout_p=0.0,
-                seed=None):
+                seed=None, n_kv_head=None):
         total, C3 = qkv.shape
-        C = C3 // 3
-        q, k, v = (_heads2(t, n_head) for t in qkv.split(C, dim=1))
+        Hk = n_head if n_kv_head is None else n_kv_head
+        C = C3 // (n_head + 2 * Hk) * n_head
+        q, k, v = _qkv_heads(qkv, n_head, Hk, _heads2)
         tmap = _varlen_plan(cu_seqlens, total)
         y = torch.empty((total, C), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((n_head, total), dtype=torch.float32,
                           device=qkv.device)
         ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
-        ctx.dropout_p = dropout_p
+        ctx.dropout_p, ctx.n_kv_head = dropout_p, Hk
         _launch_varlen_fwd(q, k, v, _heads2(y, n_head), lse, tmap,
                            cu_seqlens.numel() - 1, scale, causal=causal,
                            **_drop_kw(ctx, seed))
@@ -578,15 +661,14 @@ class _FlashAttnQkvVarlenFn(torch.autograd.Function):
     def backward(ctx, dy):
         qkv, y, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
         H = ctx.n_head
-        C = y.shape[1]
-        q, k, v = (_heads2(t, H) for t in qkv.split(C, dim=1))
+        q, k, v = _qkv_heads(qkv, H, ctx.n_kv_head, _heads2)
         dqkv = torch.empty_like(qkv)
-        dq, dk, dv = (_heads2(t, H) for t in dqkv.split(C, dim=1))
+        dq, dk, dv = _qkv_heads(dqkv, H, ctx.n_kv_head, _heads2)
         _launch_varlen_bwd(q, k, v, _heads2(y, H), _heads2(dy, H), lse, dq,
                            dk, dv, tmap, cu_seqlens.numel() - 1, ctx.scale,
                            causal=ctx.causal,
                            **_drop_kw(ctx, seed[0] if seed else None))
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def _varlen_mask(cu_seqlens: torch.Tensor, total: int,
@@ -608,8 +690,9 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                            dropout_p: float = 0.0, scale: float = None,
                            dropout_seed: Optional[torch.Tensor] = None
                            ) -> torch.Tensor:
-    """Self-attention over sequences packed back to back. q, k, v:
-    [total,H,D] (any row and head strides); cu_seqlens: int32 [n_seqs + 1]
+    """Self-attention over sequences packed back to back. q: [total,H,D],
+    k, v: [total,Hk,D] with H % Hk == 0, query head h reading K/V head
+    h // (H // Hk) (any row and head strides); cu_seqlens: int32 [n_seqs + 1]
     on the same device, sequence i owning rows cu_seqlens[i] ..
     cu_seqlens[i+1]-1. A row attends only inside its own sequence (and to
     keys at or before itself when causal). Returns [total,H,D].
@@ -623,10 +706,10 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     padding, no host sync; dropout mask plane seq * H + h with q and k
     counted from the sequence start); anything else runs torch SDPA under
     the block-diagonal mask, with torch's dropout."""
-    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
-        raise ValueError("flash_attention_varlen: q, k, v must be "
-                         "[total,H,D] of one shape, got "
-                         f"{tuple(q.shape)}, {tuple(k.shape)}, "
+    if q.dim() != 3 or not _gqa_shapes_ok(q, k, v, 1):
+        raise ValueError("flash_attention_varlen: need q [total,H,D] and "
+                         "k, v [total,Hk,D] of one shape with H % Hk == 0, "
+                         f"got {tuple(q.shape)}, {tuple(k.shape)}, "
                          f"{tuple(v.shape)}")
     _check_cu_seqlens("flash_attention_varlen", cu_seqlens, q.device)
     if fa_varlen_supported(q, k, v, cu_seqlens, causal, dropout_p):
@@ -636,37 +719,44 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens, s, causal,
                                         dropout_p, seed)
     mask = _varlen_mask(cu_seqlens, q.shape[0], causal)
+    gqa = {"enable_gqa": True} if k.shape[1] != q.shape[1] else {}
     y = torch.nn.functional.scaled_dot_product_attention(
         _rows4(q), _rows4(k), _rows4(v), attn_mask=mask,
-        dropout_p=dropout_p, scale=scale)
+        dropout_p=dropout_p, scale=scale, **gqa)
     return y.squeeze(0).transpose(0, 1)
 
 
 def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
                                cu_seqlens: torch.Tensor,
                                dropout_p: float = 0.0, causal: bool = True,
-                               dropout_seed: Optional[torch.Tensor] = None
+                               dropout_seed: Optional[torch.Tensor] = None,
+                               n_kv_head: Optional[int] = None
                                ) -> torch.Tensor:
     """``flash_attention_varlen`` on the packed projection qkv [total,3C]
-    (q, k, v thirds, heads contiguous within each); returns [total,C]. The
+    (q, k, v thirds, heads contiguous within each); returns [total,C]. With
+    n_kv_head = Hk the row is (H + 2*Hk)*D wide, as in
+    ``flash_attention_qkv``, and the result [total,H*D]. The
     qualifying case (bf16, head_dim 64 or 128, contiguous, dropout_p < 1)
     runs the kernels directly on the packed layout with no copies; anything else
     composes ``flash_attention_varlen`` from views. cu_seqlens: see there."""
-    if qkv.dim() != 2 or qkv.shape[1] % (3 * n_head):
+    Hk = _kv_heads("flash_attention_qkv_varlen", n_head, n_kv_head)
+    W = n_head + 2 * Hk
+    if qkv.dim() != 2 or qkv.shape[1] % W:
         raise ValueError("flash_attention_qkv_varlen: qkv must be "
-                         f"[total, 3 * n_head * D], got {tuple(qkv.shape)}")
+                         "[total, (n_head + 2 * n_kv_head) * D], got "
+                         f"{tuple(qkv.shape)}")
     _check_cu_seqlens("flash_attention_qkv_varlen", cu_seqlens, qkv.device)
     total, C3 = qkv.shape
-    C = C3 // 3
-    if fa_qkv_varlen_supported(qkv, n_head, cu_seqlens, dropout_p, causal):
-        scale = 1.0 / math.sqrt(C // n_head)
+    D = C3 // W
+    if fa_qkv_varlen_supported(qkv, n_head, cu_seqlens, dropout_p, causal,
+                               Hk):
+        scale = 1.0 / math.sqrt(D)
         seed = (_seed_tensor(dropout_seed, qkv.device) if dropout_p > 0.0
                 else None)
         return _FlashAttnQkvVarlenFn.apply(qkv, n_head, cu_seqlens, scale,
-                                           causal, dropout_p, seed)
-    q, k, v = (t.view(total, n_head, C // n_head)
-               for t in qkv.split(C, dim=1))
+                                           causal, dropout_p, seed, Hk)
+    q, k, v = (t.view(total, -1, D) for t in _qkv_parts(qkv, n_head, Hk))
     y = flash_attention_varlen(q, k, v, cu_seqlens, causal=causal,
                                dropout_p=dropout_p,
                                dropout_seed=dropout_seed)
-    return y.contiguous().view(total, C)
+    return y.contiguous().view(total, n_head * D)

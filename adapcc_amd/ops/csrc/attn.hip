@@ -21,7 +21,8 @@
 // backward splits FA2-style into a dq kernel (q-tile outer) and a dkv
 // kernel (kv-tile outer), both recomputing P from the saved logsumexp.
 //
-// The three kernels are templates on <kHD, kCausal, kRagged, kDrop, kVarlen>.
+// The three kernels are templates on <kHD, kCausal, kRagged, kDrop, kVarlen,
+// kGqa>.
 // <64,true,false,false,false> is the GPT-2 case.
 // kHD is the head dimension, 64 or 128. A 128-wide row is two blocks of 64
 // columns and a 64-row tile two of attn_frag.h's row images side by side,
@@ -68,6 +69,20 @@
 // in the dkv kernel q rows >= S get P = dS = 0. A valid row then computes
 // bit for bit what the fixed-length causal kernel computes for it on the
 // sequence zero-padded to a multiple of 128.
+// kGqa is grouped-query (multi-query) attention: k, v, dk, dv have Hk =
+// H / G heads, G a runtime integer > 1 (G == 1 launches the kGqa=false
+// instantiations, which are instruction for instruction the kernels without
+// the parameter), and query head h reads K/V head h / G. In the forward and
+// the dq kernel that is the whole change: grid, q, o, dO, dq, lse, delta
+// and the dropout plane b*H + h stay by query head. The dkv kernel's grid
+// counts K/V heads; a workgroup loads the K/V fragments of its k tile once
+// and walks the q tiles of the group's G query heads in turn, one flattened
+// (head, tile) loop whose last tile of a head prefetches the first of the
+// next, so the double buffer runs through. dV and dK accumulate over all of
+// them in fp32 and one epilogue rounds the group sum once: no atomics, no
+// second pass, deterministic. What moves from head to head is wave-uniform:
+// the q, dO, lse and delta planes, the mask plane of the staged q parts,
+// and (per lane, recomputed at each head) the k part of the mask word.
 //
 // Reference parity note: the reference (JoeyYoung/adapcc) has no attention
 // kernels (models used stock torch); this op exists to meet BASELINE.json's
@@ -125,6 +140,8 @@ struct FaParams {
   // variable-length mode, kVarlen instantiations only (both directions)
   const int4* tmap;    // [gridDim.x] (seq, tile, start, len), seq < 0: unused
   int total;           // packed rows; lse and delta are [H, total]
+  // grouped-query mode, kGqa instantiations only (both directions)
+  int G;               // query heads per K/V head: k, v, dk, dv have H/G heads
 };
 
 // Variable-length mode: q, k, v, ... are [total, H, kHD] views that hold the
@@ -152,6 +169,15 @@ __device__ __forceinline__ T* seq_plane(T* x, const TStride& s, int b, int h,
     return x + (long)h * s.sh + row0 * s.ss;
   else
     return plane(x, s, b, h);
+}
+
+// K/V head of query head h: h itself, or in the grouped-query mode h / G.
+template <bool kGqa>
+__device__ __forceinline__ int kv_head(int h, int G) {
+  if constexpr (kGqa)
+    return h / G;
+  else
+    return h;
 }
 
 // An entry the plan left unused (or, should the map ever be stale, a tile
@@ -348,10 +374,10 @@ __device__ __forceinline__ float ds_elem(float pe, float dp, float delta,
 // ---------------------------------------------------------------------------
 // Forward.
 // Grid: (ceil(S/128), B*H); block 256 = 4 waves, wave w owns q rows
-// qt*128 + w*32 .. +31.
+// qt*128 + w*32 .. +31. kGqa: k and v are read at head h / G.
 // ---------------------------------------------------------------------------
 template <int kHD, bool kCausal, bool kRagged, bool kDrop,
-          bool kVarlen = false>
+          bool kVarlen = false, bool kGqa = false>
 __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_fwd_kernel(
     FaParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -390,8 +416,9 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_fwd_kernel(
   }
 
   const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
-  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
-  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  const int hk = kv_head<kGqa>(h, p.G);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, hk, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, hk, row0);
   __bf16* og = seq_plane<kVarlen>(p.o, p.os, b, h, row0);
   float* lseg =
       p.lse + (kVarlen ? (long)h * p.total + row0 : (long)bh * S);
@@ -631,7 +658,7 @@ __device__ __forceinline__ float dot8_tree(bf16x8 a, bf16x8 b) {
 }
 
 template <int kHD, bool kCausal, bool kRagged, bool kDrop,
-          bool kVarlen = false>
+          bool kVarlen = false, bool kGqa = false>
 __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_bwd_dq_kernel(
     FaParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -668,8 +695,9 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_bwd_dq_kernel(
   }
 
   const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
-  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
-  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  const int hk = kv_head<kGqa>(h, p.G);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, hk, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, hk, row0);
   const __bf16* dog = seq_plane<kVarlen>(p.dout, p.dos_, b, h, row0);
   const __bf16* og = seq_plane<kVarlen>(p.o, p.os, b, h, row0);
   __bf16* dqg = seq_plane<kVarlen>(p.dq, p.dqs, b, h, row0);
@@ -851,8 +879,9 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_bwd_dq_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Backward dK/dV. Grid (ceil(S/128), B*H); wave owns kv rows kt*128+w*32..+31,
-// loops q tiles >= the diagonal (causal) or all q tiles:
+// Backward dK/dV. Grid (ceil(S/128), B*H), kGqa: B*Hk; wave owns kv rows
+// kt*128+w*32..+31, loops q tiles >= the diagonal (causal) or all q tiles
+// (kGqa: of each of the group's G query heads in turn):
 //   S = Q·K^T   as C[q][k]: A=Q row frags (LDS), B=K direct (registers)
 //   P^T[k][q] = exp2(S*c1 - lse[q]*log2e) masked            lane-k local
 //   dP[q][k]: A=dO row frags, B=V^T direct (registers)
@@ -860,7 +889,7 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_bwd_dq_kernel(
 //   dS^T = P^T*(dP-D[q])*scale;  dK += dS^T·Q (A=packed dS^T, B=Q^T tr)
 // ---------------------------------------------------------------------------
 template <int kHD, bool kCausal, bool kRagged, bool kDrop,
-          bool kVarlen = false>
+          bool kVarlen = false, bool kGqa = false>
 __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
     FaParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -884,27 +913,41 @@ __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   int kt = blockIdx.x, bh = blockIdx.y, b, h, S = p.S;  // as in the forward
+  // grouped-query mode: y counts K/V heads, hk is this workgroup's, and h,
+  // bh start at the first of its G query heads, hk*G .. hk*G + G-1
+  int hk;
   long row0 = 0;
   if constexpr (kVarlen) {
     const VarlenTile vt = varlen_tile(p);
     if (varlen_idle(vt)) return;
     kt = vt.tile;
     b = 0;
-    h = blockIdx.y;
+    hk = blockIdx.y;
+    h = kGqa ? hk * p.G : hk;
     bh = vt.seq * p.H + h;
     S = vt.len;
     row0 = vt.start;
+  } else if constexpr (kGqa) {
+    const int Hk = p.H / p.G;
+    b = bh / Hk;
+    hk = bh % Hk;
+    h = hk * p.G;
+    bh = b * p.H + h;
   } else {
     b = bh / p.H;
     h = bh % p.H;
+    hk = h;
   }
 
+  // kGqa: qg, dog, lseg, deltag (and bh) are those of the head the staging
+  // is at; they move on to the group's next query head when the prefetch
+  // does (below)
   const __bf16* qg = seq_plane<kVarlen>(p.q, p.qs, b, h, row0);
-  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, h, row0);
-  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, h, row0);
+  const __bf16* kg = seq_plane<kVarlen>(p.k, p.ks, b, hk, row0);
+  const __bf16* vg = seq_plane<kVarlen>(p.v, p.vs, b, hk, row0);
   const __bf16* dog = seq_plane<kVarlen>(p.dout, p.dos_, b, h, row0);
-  __bf16* dkg = seq_plane<kVarlen>(p.dk, p.dks, b, h, row0);
-  __bf16* dvg = seq_plane<kVarlen>(p.dv, p.dvs, b, h, row0);
+  __bf16* dkg = seq_plane<kVarlen>(p.dk, p.dks, b, hk, row0);
+  __bf16* dvg = seq_plane<kVarlen>(p.dv, p.dvs, b, hk, row0);
   const long lrow0 = kVarlen ? (long)h * p.total + row0 : (long)bh * S;
   const float* lseg = p.lse + lrow0;
   const float* deltag = p.delta + lrow0;
@@ -938,11 +981,22 @@ __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
 
   // dropout: this lane's k part; seed_lo feeds the tiles' q parts
   [[maybe_unused]] unsigned dkb = 0, seed_lo = 0;
+  // kGqa: the k part belongs to the plane, so each head of the group gets
+  // its own when the tile loop reaches it; bhc is the plane the loop is at
+  [[maybe_unused]] unsigned seed_hi = 0;
+  [[maybe_unused]] int bhc = bh;
   if constexpr (kDrop) {
     const unsigned long sd = (unsigned long)*p.seed;
     seed_lo = (unsigned)sd;
     dkb = drop_k_part((unsigned)(sd >> 32), bh, krow);
+    if constexpr (kGqa) seed_hi = (unsigned)(sd >> 32);
   }
+  // kGqa: heads of the group still to be staged / still to be walked after
+  // the current one. The tile loop below is the flattened (head, tile)
+  // iteration: the last tile of a head prefetches tile t0 of the next, so
+  // the double buffer never drains inside a workgroup.
+  [[maybe_unused]] int stage_left = 0, walk_left = 0;
+  if constexpr (kGqa) stage_left = walk_left = p.G - 1;
 
   // stage q/dO tile t0 and its side tile
   {
@@ -966,9 +1020,24 @@ __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
   for (int t = t0; t < n64; ++t) {
     RowTile<kHD> nq, nd;
     SideVal ns = {0.f, 0.f};
-    const bool pref = t + 1 < n64;
+    bool pref = t + 1 < n64;
+    int tn = t + 1;  // the tile to prefetch
+    if constexpr (kGqa) {
+      if (!pref && stage_left > 0) {
+        // last tile of a head: go on to tile t0 of the group's next head,
+        // one plane on in q, dO, lse, delta and the mask (wave-uniform)
+        --stage_left;
+        pref = true;
+        tn = t0;
+        qg += p.qs.sh;
+        dog += p.dos_.sh;
+        lseg += kVarlen ? p.total : S;
+        deltag += kVarlen ? p.total : S;
+        ++bh;
+      }
+    }
     if (pref) {
-      const int qb1 = (t + 1) * 64;
+      const int qb1 = tn * 64;
       const long r0 = ld_row32<kRagged>(qb1 + srow, S);
       const long r1 = ld_row32<kRagged>(qb1 + srow + 32, S);
       nq = ld_tile<kHD>(qg, p.qs.ss, r0, r1, scol);
@@ -1080,6 +1149,15 @@ __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
     }
     __syncthreads();
     cur ^= 1;
+    if constexpr (kGqa) {
+      if (t + 1 == n64 && walk_left > 0) {
+        // the next head's tile t0 is staged: walk it with that plane's
+        // k part; dvacc*/dkacc* carry on, which forms the group sum
+        --walk_left;
+        t = t0 - 1;
+        if constexpr (kDrop) dkb = drop_k_part(seed_hi, ++bhc, krow);
+      }
+    }
   }
 
   // epilogue: C[k-rows][d=lane&31] per accumulator -> round-trip through
@@ -1294,10 +1372,16 @@ void with_mode(bool causal, int S, bool drop, bool varlen, F&& f) {
 
 // The part of the parameter block that both directions fill. strides: 3 per
 // tensor, q, k, v, o first.
-FaParams fwd_params(const void* q, const void* k, const void* v, void* o,
-                    float* lse, int H, int S, const long* strides,
-                    float scale) {
+FaParams fwd_params(const char* name, const void* q, const void* k,
+                    const void* v, void* o, float* lse, int H, int n_kv_head,
+                    int S, const long* strides, float scale) {
+  const int Hk = n_kv_head == 0 ? H : n_kv_head;
+  if (H < 1 || Hk < 1 || H % Hk != 0)
+    throw std::runtime_error(std::string(name) + ": need n_kv_head >= 1 that "
+                             "divides H, got H " + std::to_string(H) +
+                             ", n_kv_head " + std::to_string(n_kv_head));
   FaParams p = {};
+  p.G = H / Hk;
   p.q = (const __bf16*)q;
   p.k = (const __bf16*)k;
   p.v = (const __bf16*)v;
@@ -1346,30 +1430,49 @@ void with_head_dim(const char* name, int head_dim, F&& f) {
                              std::to_string(head_dim));
 }
 
+// Calls f(kGqa): G == 1 runs the instantiations without the flag, which are
+// the kernels from before it.
+template <typename F>
+void with_gqa(int G, F&& f) {
+  if (G > 1)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
 void launch_fwd(const FaParams& p, dim3 grid, int head_dim, bool causal,
                 bool drop, bool varlen, hipStream_t stream) {
   with_head_dim("fa_forward", head_dim, [&](auto hd) {
     with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
-      constexpr int kHD = decltype(hd)::value;
-      constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                     kD = decltype(d)::value, kV = decltype(vl)::value;
-      hipLaunchKernelGGL((fa_fwd_kernel<kHD, kC, kR, kD, kV>), grid,
-                         dim3(256), 0, stream, p);
+      with_gqa(p.G, [&](auto gq) {
+        constexpr int kHD = decltype(hd)::value;
+        constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                       kD = decltype(d)::value, kV = decltype(vl)::value,
+                       kG = decltype(gq)::value;
+        hipLaunchKernelGGL((fa_fwd_kernel<kHD, kC, kR, kD, kV, kG>), grid,
+                           dim3(256), 0, stream, p);
+      });
     });
   });
 }
 
+// grid: that of the dq kernel, heads in y; the dkv kernel's y counts K/V
+// heads, each workgroup walking the G query heads of its group.
 void launch_bwd(const FaParams& p, dim3 grid, int head_dim, bool causal,
                 bool drop, bool varlen, hipStream_t stream) {
+  const dim3 kv_grid(grid.x, grid.y / p.G);
   with_head_dim("fa_backward", head_dim, [&](auto hd) {
     with_mode(causal, p.S, drop, varlen, [&](auto c, auto r, auto d, auto vl) {
-      constexpr int kHD = decltype(hd)::value;
-      constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
-                     kD = decltype(d)::value, kV = decltype(vl)::value;
-      hipLaunchKernelGGL((fa_bwd_dq_kernel<kHD, kC, kR, kD, kV>), grid,
-                         dim3(256), 0, stream, p);
-      hipLaunchKernelGGL((fa_bwd_dkv_kernel<kHD, kC, kR, kD, kV>), grid,
-                         dim3(256), 0, stream, p);
+      with_gqa(p.G, [&](auto gq) {
+        constexpr int kHD = decltype(hd)::value;
+        constexpr bool kC = decltype(c)::value, kR = decltype(r)::value,
+                       kD = decltype(d)::value, kV = decltype(vl)::value,
+                       kG = decltype(gq)::value;
+        hipLaunchKernelGGL((fa_bwd_dq_kernel<kHD, kC, kR, kD, kV, kG>), grid,
+                           dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((fa_bwd_dkv_kernel<kHD, kC, kR, kD, kV, kG>),
+                           kv_grid, dim3(256), 0, stream, p);
+      });
     });
   });
 }
@@ -1384,15 +1487,19 @@ unsigned fa_drop_threshold(double p) { return drop_threshold(p); }
 // o row, is 64 or 128; anything else throws. dropout_p == 0 launches the
 // kDrop=false instantiations, which are the kernels without dropout, and
 // never touches seed; dropout_p > 0 reads the 64-bit seed at `seed` (device
-// memory) when the kernel runs.
+// memory) when the kernel runs. n_kv_head is the number of heads of k, v
+// (and dk, dv); 0 means H. It must divide H, and query head h then reads
+// K/V head h / (H / n_kv_head).
 // ---------------------------------------------------------------------------
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
-                double dropout_p, const long* seed, int head_dim) {
+                double dropout_p, const long* seed, int head_dim,
+                int n_kv_head) {
   check_len("fa_forward", S, causal);
   check_drop("fa_forward", dropout_p, seed);
-  FaParams p = fwd_params(q, k, v, o, lse, H, S, strides, scale);
+  FaParams p = fwd_params("fa_forward", q, k, v, o, lse, H, n_kv_head, S,
+                          strides, scale);
   set_drop(p, dropout_p, seed);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
   launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, false, stream);
@@ -1404,11 +1511,13 @@ void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
-                 double dropout_p, const long* seed, int head_dim) {
+                 double dropout_p, const long* seed, int head_dim,
+                 int n_kv_head) {
   check_len("fa_backward", S, causal);
   check_drop("fa_backward", dropout_p, seed);
-  FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
-                          const_cast<float*>(lse), H, S, strides, scale);
+  FaParams p = fwd_params("fa_backward", q, k, v, const_cast<void*>(o),
+                          const_cast<float*>(lse), H, n_kv_head, S, strides,
+                          scale);
   set_drop(p, dropout_p, seed);
   bwd_params(p, do_, delta, dq, dk, dv, strides);
   const dim3 grid((S + kQT - 1) / kQT, B * H);
@@ -1436,10 +1545,11 @@ void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
                        float* lse, const int* tmap, int total, int n_seqs,
                        int H, const long* strides, float scale,
                        hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed, int head_dim) {
+                       const long* seed, int head_dim, int n_kv_head) {
   check_varlen("fa_varlen_forward", total, n_seqs, H);
   check_drop("fa_varlen_forward", dropout_p, seed);
-  FaParams p = fwd_params(q, k, v, o, lse, H, 0, strides, scale);
+  FaParams p = fwd_params("fa_varlen_forward", q, k, v, o, lse, H, n_kv_head,
+                          0, strides, scale);
   set_drop(p, dropout_p, seed);
   set_varlen(p, tmap, total);
   const dim3 grid(varlen_max_tiles(total, n_seqs), H);
@@ -1452,11 +1562,12 @@ void fa_varlen_backward(const void* q, const void* k, const void* v,
                         const int* tmap, int total, int n_seqs, int H,
                         const long* strides, float scale, hipStream_t stream,
                         bool causal, double dropout_p, const long* seed,
-                        int head_dim) {
+                        int head_dim, int n_kv_head) {
   check_varlen("fa_varlen_backward", total, n_seqs, H);
   check_drop("fa_varlen_backward", dropout_p, seed);
-  FaParams p = fwd_params(q, k, v, const_cast<void*>(o),
-                          const_cast<float*>(lse), H, 0, strides, scale);
+  FaParams p = fwd_params("fa_varlen_backward", q, k, v,
+                          const_cast<void*>(o), const_cast<float*>(lse), H,
+                          n_kv_head, 0, strides, scale);
   set_drop(p, dropout_p, seed);
   set_varlen(p, tmap, total);
   bwd_params(p, do_, delta, dq, dk, dv, strides);

@@ -101,12 +101,14 @@ void ce_backward(int dtype, const void* logits, const void* targets,
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
-                double dropout_p, const long* seed, int head_dim);
+                double dropout_p, const long* seed, int head_dim,
+                int n_kv_head);
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
-                 double dropout_p, const long* seed, int head_dim);
+                 double dropout_p, const long* seed, int head_dim,
+                 int n_kv_head);
 void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
                      double dropout_p, hipStream_t stream);
 void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
@@ -115,14 +117,14 @@ void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
                        float* lse, const int* tmap, int total, int n_seqs,
                        int H, const long* strides, float scale,
                        hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed, int head_dim);
+                       const long* seed, int head_dim, int n_kv_head);
 void fa_varlen_backward(const void* q, const void* k, const void* v,
                         const void* o, const void* do_, const float* lse,
                         float* delta, void* dq, void* dk, void* dv,
                         const int* tmap, int total, int n_seqs, int H,
                         const long* strides, float scale, hipStream_t stream,
                         bool causal, double dropout_p, const long* seed,
-                        int head_dim);
+                        int head_dim, int n_kv_head);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -284,30 +286,33 @@ PYBIND11_MODULE(_core, m) {
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            int B, int H, int S, const std::vector<long>& strides, float scale,
            uintptr_t stream, bool causal, double dropout_p, uintptr_t seed,
-           int head_dim) {
+           int head_dim, int n_kv_head) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_fwd: need 12 strides");
           adapcc::fa_forward((const void*)q, (const void*)k, (const void*)v,
                              (void*)o, (float*)lse, B, H, S, strides.data(),
                              scale, reinterpret_cast<hipStream_t>(stream),
-                             causal, dropout_p, (const long*)seed, head_dim);
+                             causal, dropout_p, (const long*)seed, head_dim,
+                             n_kv_head);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
         // causal=False: non-causal self-attention, any S >= 1.
         // dropout_p > 0: seed is the address of one int64 in device memory
         // head_dim: 64 or 128, the width of a q/k/v/o row
+        // n_kv_head: heads of k and v (grouped-query attention), 0 = H
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("S"),
         py::arg("strides"), py::arg("scale"), py::arg("stream"),
         py::arg("causal") = true, py::arg("dropout_p") = 0.0,
-        py::arg("seed") = 0, py::arg("head_dim") = 64);
+        py::arg("seed") = 0, py::arg("head_dim") = 64,
+        py::arg("n_kv_head") = 0);
   m.def("fa_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, int B, int H, int S, const std::vector<long>& strides,
            float scale, uintptr_t stream, bool causal, double dropout_p,
-           uintptr_t seed, int head_dim) {
+           uintptr_t seed, int head_dim, int n_kv_head) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_bwd: need 24 strides");
           adapcc::fa_backward((const void*)q, (const void*)k, (const void*)v,
@@ -315,7 +320,8 @@ PYBIND11_MODULE(_core, m) {
                               (const float*)lse, (float*)delta, (void*)dq,
                               (void*)dk, (void*)dv, B, H, S, strides.data(),
                               scale, reinterpret_cast<hipStream_t>(stream),
-                              causal, dropout_p, (const long*)seed, head_dim);
+                              causal, dropout_p, (const long*)seed, head_dim,
+                              n_kv_head);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -325,7 +331,7 @@ PYBIND11_MODULE(_core, m) {
         py::arg("S"), py::arg("strides"), py::arg("scale"),
         py::arg("stream"), py::arg("causal") = true,
         py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("head_dim") = 64);
+        py::arg("head_dim") = 64, py::arg("n_kv_head") = 0);
   // out: [B,H,S,S] uint8, 1 where the attention kernels keep the element
   m.def("fa_dropout_mask",
         [](uintptr_t out, uintptr_t seed, int B, int H, int S,
@@ -358,14 +364,15 @@ PYBIND11_MODULE(_core, m) {
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            uintptr_t tmap, int total, int n_seqs, int H,
            const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed, int head_dim) {
+           bool causal, double dropout_p, uintptr_t seed, int head_dim,
+           int n_kv_head) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_varlen_fwd: need 12 strides");
           adapcc::fa_varlen_forward(
               (const void*)q, (const void*)k, (const void*)v, (void*)o,
               (float*)lse, (const int*)tmap, total, n_seqs, H, strides.data(),
               scale, reinterpret_cast<hipStream_t>(stream), causal, dropout_p,
-              (const long*)seed, head_dim);
+              (const long*)seed, head_dim, n_kv_head);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -373,13 +380,15 @@ PYBIND11_MODULE(_core, m) {
         py::arg("lse"), py::arg("tmap"), py::arg("total"), py::arg("n_seqs"),
         py::arg("H"), py::arg("strides"), py::arg("scale"), py::arg("stream"),
         py::arg("causal") = true, py::arg("dropout_p") = 0.0,
-        py::arg("seed") = 0, py::arg("head_dim") = 64);
+        py::arg("seed") = 0, py::arg("head_dim") = 64,
+        py::arg("n_kv_head") = 0);
   m.def("fa_varlen_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, uintptr_t tmap, int total, int n_seqs, int H,
            const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed, int head_dim) {
+           bool causal, double dropout_p, uintptr_t seed, int head_dim,
+           int n_kv_head) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_varlen_bwd: need 24 strides");
           adapcc::fa_varlen_backward(
@@ -387,7 +396,7 @@ PYBIND11_MODULE(_core, m) {
               (const void*)dout, (const float*)lse, (float*)delta, (void*)dq,
               (void*)dk, (void*)dv, (const int*)tmap, total, n_seqs, H,
               strides.data(), scale, reinterpret_cast<hipStream_t>(stream),
-              causal, dropout_p, (const long*)seed, head_dim);
+              causal, dropout_p, (const long*)seed, head_dim, n_kv_head);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -397,7 +406,7 @@ PYBIND11_MODULE(_core, m) {
         py::arg("n_seqs"), py::arg("H"), py::arg("strides"),
         py::arg("scale"), py::arg("stream"), py::arg("causal") = true,
         py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("head_dim") = 64);
+        py::arg("head_dim") = 64, py::arg("n_kv_head") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

@@ -2,7 +2,7 @@
 
 Run on a GPU box:  python benchmarks/attn_bench.py
                        [--shape gpt2|vit|gpt2-d128|vit-d128|varlen]
-                       [--dropout P] [--head-dim 64|128]
+                       [--dropout P] [--head-dim 64|128] [--kv-heads N]
 
 gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
 (ViT-base at 224 px). gpt2-d128: B32 H16 S1024 D128, causal; vit-d128: B64 H8
@@ -15,6 +15,12 @@ a seeded mix of lengths drawn log-uniformly in [16, 1024] against the same
 documents padded to 1024 and against SDPA under a dense block-diagonal mask
 (what the mode is for), and the plan kernel by itself. --head-dim 128 (varlen
 only) runs the same token count as H6 D128.
+--kv-heads N (the fixed shapes and varlen): grouped-query attention with N
+K/V heads. Times, alternating in one process, (a) the GQA call, (b) what
+GQA costs without it: K/V repeat_interleave'd to H heads in front of the
+same kernels and autograd summing dk/dv over the group, with those passes
+and (K/V expanded beforehand, per-head dk/dv left as they are) without, and
+(c) torch SDPA with enable_gqa=True.
 """
 import argparse
 import math
@@ -59,12 +65,19 @@ def main():
                     help="attention dropout rate for both paths")
     ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64,
                     help="varlen only: 128 halves the heads, same tokens")
+    ap.add_argument("--kv-heads", type=int, default=0,
+                    help="K/V heads (must divide the shape's heads): the "
+                         "grouped-query comparison instead of the usual one")
     args = ap.parse_args()
     drop = args.dropout
     if args.shape == "varlen":
-        return varlen_path(args.iters or 20, drop,
-                           H=12 * 64 // args.head_dim, D=args.head_dim)
+        H = 12 * 64 // args.head_dim
+        if args.kv_heads:
+            return gqa_varlen_path(H, args.kv_heads, args.head_dim, drop)
+        return varlen_path(args.iters or 20, drop, H=H, D=args.head_dim)
     B, H, S, D, causal = SHAPES[args.shape]
+    if args.kv_heads:
+        return gqa_path(B, H, args.kv_heads, S, D, causal, drop)
     iters = args.iters or (200 if args.shape.startswith("vit") else 20)
 
     scale = 1.0 / math.sqrt(D)
@@ -127,6 +140,168 @@ def layer_path(B, H, S, D, causal, fwd_flops, bwd_flops, iters, drop=0.0):
 
         ms = bench(fb, iters)
         print(f"{name} f+b:  {ms:7.3f} ms  {(fwd_flops+bwd_flops)/ms/1e9:8.1f} TF/s")
+
+
+def alternate(fns, window=0.5, rounds=5):
+    """Times the callables of `fns` (name -> fn) against each other: after
+    a warmup of each, `rounds` rounds that run every candidate in turn for
+    window/rounds seconds' worth of calls (from a first estimate), each
+    block ended by a synchronise. Returns name -> (mean ms per call over
+    all rounds, fastest round, slowest round)."""
+    calls = {}
+    for name, fn in fns.items():
+        ms = bench(fn, iters=3, warmup=3)
+        calls[name] = max(2, int(math.ceil(window / rounds * 1e3 / ms)))
+    per_round = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            per_round[name].append(bench(fn, iters=calls[name], warmup=0))
+    return {name: (sum(r) / len(r), min(r), max(r))
+            for name, r in per_round.items()}
+
+
+def report(title, res, flops):
+    print(title)
+    base = res["gqa"][0]
+    for name, (ms, lo, hi) in res.items():
+        print(f"  {name:<26} {ms:8.3f} ms  (rounds {lo:.3f}..{hi:.3f})  "
+              f"{flops / ms / 1e9:7.1f} TF/s  gqa/this {base / ms:.3f}")
+
+
+def gqa_candidates(q, k, v, g, attn, sdpa):
+    """name -> (forward fn, forward+backward fn). attn(q, k, v) is the
+    project's call, sdpa(q, k, v) torch's with enable_gqa; the head
+    dimension is 1."""
+    G = q.shape[1] // k.shape[1]
+    ke = k.detach().repeat_interleave(G, dim=1).requires_grad_(True)
+    ve = v.detach().repeat_interleave(G, dim=1).requires_grad_(True)
+
+    def expanded(q, k, v):
+        return attn(q, k.repeat_interleave(G, dim=1),
+                    v.repeat_interleave(G, dim=1))
+
+    out = {}
+    for name, f, kk, vv in (("gqa", attn, k, v),
+                            ("expanded + passes", expanded, k, v),
+                            ("expanded, kernels only", attn, ke, ve),
+                            ("sdpa enable_gqa", sdpa, k, v)):
+        if f is None:
+            continue
+
+        def fwd(f=f, kk=kk, vv=vv):
+            return f(q, kk, vv)
+
+        def fb(f=f, kk=kk, vv=vv):
+            q.grad = kk.grad = vv.grad = None
+            f(q, kk, vv).backward(g)
+
+        out[name] = (fwd, fb)
+    return out
+
+
+def run_gqa(cands, fwd_flops, bwd_flops):
+    report("forward", alternate({n: c[0] for n, c in cands.items()}),
+           fwd_flops)
+    report("forward + backward",
+           alternate({n: c[1] for n, c in cands.items()}),
+           fwd_flops + bwd_flops)
+
+
+def gqa_path(B, H, Hk, S, D, causal, drop):
+    from adapcc_amd.ops.attention import fa_supported, flash_attention
+
+    assert H % Hk == 0 and Hk < H
+    torch.manual_seed(0)
+
+    def make(h):
+        return torch.randn(B, h, S, D, device="cuda", dtype=torch.bfloat16,
+                           requires_grad=True)
+
+    q, k, v = make(H), make(Hk), make(Hk)
+    g = torch.randn(B, H, S, D, device="cuda", dtype=torch.bfloat16)
+    # a missing kernel is an error here, not a silent SDPA-vs-SDPA run
+    assert fa_supported(q, k, v, causal, drop)
+    fwd_flops = 4 * B * H * S * S * D / (2 if causal else 1)
+    kv_bytes = 2 * B * Hk * S * D * 2
+    print(f"B{B} H{H} Hk{Hk} (G={H // Hk}) S{S} D{D} causal={causal} "
+          f"dropout={drop}")
+    print(f"tile-loop FLOPs (as MHA): fwd {fwd_flops / 1e9:.1f} G, bwd "
+          f"{2.5 * fwd_flops / 1e9:.1f} G; K+V bytes {kv_bytes / 2**20:.0f} "
+          f"MiB (expanded: {kv_bytes * (H // Hk) / 2**20:.0f} MiB)")
+
+    def attn(q, k, v):
+        return flash_attention(q, k, v, causal=causal, dropout_p=drop)
+
+    def sdpa(q, k, v):
+        return torch.nn.functional.scaled_dot_product_attention(
+            q, k, v, is_causal=causal, dropout_p=drop, enable_gqa=True)
+
+    run_gqa(gqa_candidates(q, k, v, g, attn, sdpa), fwd_flops,
+            2.5 * fwd_flops)
+
+
+def gqa_varlen_path(H, Hk, D, drop, tokens=131072, S=1024):
+    """The mixed lengths of varlen_path through flash_attention_varlen with
+    Hk K/V heads; SDPA (dense block-diagonal mask) on the first 8192
+    tokens' documents, where the GQA call is timed again."""
+    from adapcc_amd.ops.attention import (fa_varlen_supported,
+                                          flash_attention_varlen)
+
+    assert H % Hk == 0 and Hk < H
+    torch.manual_seed(0)
+
+    def cu_of(lens):
+        cu = torch.tensor([0] + lens, dtype=torch.int64).cumsum(0)
+        return cu.to(torch.int32).cuda()
+
+    def make(rows, h, grad=True):
+        return torch.randn(rows, h, D, device="cuda", dtype=torch.bfloat16,
+                           requires_grad=grad)
+
+    def flops(lens):
+        return sum(4 * H * n * n * D / 2 for n in lens)
+
+    lens = mixed_lengths(tokens, 16, S, seed=0)
+    sub, rows = [], 0
+    for m in lens:
+        if rows + m > 8192:
+            break
+        sub.append(m)
+        rows += m
+    for name, ls, with_sdpa in (("mixed", lens, False),
+                                ("subset for SDPA", sub, True)):
+        n = sum(ls)
+        cu = cu_of(ls)
+        q, k, v = make(n, H), make(n, Hk), make(n, Hk)
+        g = make(n, H, grad=False)
+        assert fa_varlen_supported(q, k, v, cu, True, drop)
+        kv_bytes = 2 * n * Hk * D * 2
+        print(f"{name}: {len(ls)} sequences, {n} tokens, H{H} Hk{Hk} D{D} "
+              f"causal dropout={drop}; tile-loop FLOPs (as MHA, exact "
+              f"triangles) fwd {flops(ls) / 1e9:.1f} G; K+V bytes "
+              f"{kv_bytes / 2**20:.1f} MiB (expanded: "
+              f"{kv_bytes * (H // Hk) / 2**20:.1f} MiB)")
+
+        def attn(q, k, v, cu=cu):
+            return flash_attention_varlen(q, k, v, cu, causal=True,
+                                          dropout_p=drop)
+
+        sdpa = None
+        if with_sdpa:
+            doc = torch.repeat_interleave(
+                torch.arange(len(ls), device="cuda"),
+                torch.tensor(ls, device="cuda"))
+            mask = (doc.view(-1, 1) == doc.view(1, -1)).tril_()
+
+            def sdpa(q, k, v, mask=mask):
+                y = torch.nn.functional.scaled_dot_product_attention(
+                    q.transpose(0, 1)[None], k.transpose(0, 1)[None],
+                    v.transpose(0, 1)[None], attn_mask=mask,
+                    dropout_p=drop, enable_gqa=True)
+                return y[0].transpose(0, 1)
+
+        run_gqa(gqa_candidates(q, k, v, g, attn, sdpa), flops(ls),
+                2.5 * flops(ls))
 
 
 def _fwd_and_fb(name, f, x, gy, iters):
