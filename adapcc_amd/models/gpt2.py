@@ -92,8 +92,14 @@ class MLP(nn.Module):
         self.c_proj = nn.Linear(4 * cfg.n_embd, cfg.n_embd)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        from ..ops.fused import fused_gelu
+        from ..ops.fused import fused_gelu, gelu_bias_grad_fusable
 
+        w, b = self.c_fc.weight, self.c_fc.bias
+        rows = x.numel() // max(x.shape[-1], 1)
+        if gelu_bias_grad_fusable(x.device, x.dtype, rows, w.shape[0], b):
+            # the GeLU backward sums the dx it writes into c_fc.bias' gradient
+            # (no reduce pass over dx); the GEMM still adds the bias
+            return self.c_proj(fused_gelu(F.linear(x, w, b.detach()), bias=b))
         return self.c_proj(fused_gelu(self.c_fc(x)))
 
 

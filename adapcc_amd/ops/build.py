@@ -16,9 +16,10 @@ import sysconfig
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # adapcc_amd/
 CSRC = os.path.join(PKG_DIR, "ops", "csrc")
 SOURCES = ["kernels.hip", "engine.hip", "plan.cpp", "lnorm.hip", "ce.hip",
-           "attn.hip", "attn_probe.hip", "gelu.hip", "moe.hip",
+           "attn.hip", "attn_probe.hip", "gelu.hip", "moe.hip", "colsum.hip",
            "bindings.hip"]
-HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h", "attn_drop.h"]
+HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h", "attn_drop.h",
+           "ln_cols.h"]
 OUT_SO = os.path.join(PKG_DIR, "_core.so")
 STAMP = os.path.join(PKG_DIR, "ops", ".build_stamp")
 

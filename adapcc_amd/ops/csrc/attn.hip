@@ -974,9 +974,9 @@ __global__ __launch_bounds__(256, kHD == 64 ? 2 : 1) void fa_bwd_dkv_kernel(
 
   const int srow = threadIdx.x >> 3;
   const int scol = (threadIdx.x & 7) * 8;
-  // first 64-row q tile (varlen starts at the diagonal itself: the tiles
-  // between kt and it are skipped whole by the causal cut below)
-  const int t0 = kCausal ? (kVarlen ? kt * (kQT / 64) : kt) : 0;
+  // first 64-row q tile: the diagonal's. The workgroup's keys start at row
+  // kt * kQT, and the causal cut below skips every earlier tile whole.
+  const int t0 = kCausal ? kt * (kQT / 64) : 0;
   const int n64 = (S + 63) / 64;
 
   // dropout: this lane's k part; seed_lo feeds the tiles' q parts

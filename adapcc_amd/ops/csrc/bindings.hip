@@ -95,9 +95,18 @@ void ln_dropadd_backward(int dtype, const void* dy, const void* dx_new,
 void ce_forward(int dtype, const void* logits, const void* targets,
                 float* loss, float* lse, long rows, long cols,
                 long ignore_index, hipStream_t stream);
+long ce_fused_max_cols(int dtype);
+void ce_forward_grad(int dtype, const void* logits, const void* targets,
+                     const float* g0, float* loss, float* lse, void* dlogits,
+                     long rows, long cols, long ignore_index,
+                     hipStream_t stream);
 void ce_backward(int dtype, const void* logits, const void* targets,
-                 const float* lse, const float* gscale, void* dlogits,
-                 long rows, long cols, long ignore_index, hipStream_t stream);
+                 const float* lse, const float* gscale, const float* upstream,
+                 void* dlogits, long rows, long cols, long ignore_index,
+                 hipStream_t stream);
+void colsum_fold(int out_dtype, const float* a0, const float* a1,
+                 const float* a2, void* o0, void* o1, void* o2, long nslots,
+                 long cols, hipStream_t stream);
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
@@ -130,6 +139,10 @@ void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
 void gelu_backward(int dtype, const void* x, const void* dy, void* dx, long n,
                    hipStream_t stream);
+bool gelu_bias_supported(long cols, int dtype);
+void gelu_backward_bias(int dtype, const void* x, const void* dy, void* dx,
+                        float* ws, long rows, long cols, int nblocks,
+                        hipStream_t stream);
 void moe_route(int dtype, const void* logits, float* gate_p, int* expert,
                int* slot, int* src, int* counts, int* offs, int* totals,
                long ntok, long E, long cap, hipStream_t stream);
@@ -269,14 +282,44 @@ PYBIND11_MODULE(_core, m) {
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });
+  // upstream: 0, or a device pointer to the fp32 upstream gradient; at
+  // exactly 1.0f the kernel leaves dlogits (ce_fwd_grad's) as it stands.
   m.def("ce_bwd",
         [](int dtype, uintptr_t logits, uintptr_t targets, uintptr_t lse,
-           uintptr_t gscale, uintptr_t dlogits, long rows, long cols,
-           long ignore_index, uintptr_t stream) {
+           uintptr_t gscale, uintptr_t upstream, uintptr_t dlogits, long rows,
+           long cols, long ignore_index, uintptr_t stream) {
           adapcc::ce_backward(dtype, (const void*)logits,
                               (const void*)targets, (const float*)lse,
-                              (const float*)gscale, (void*)dlogits, rows,
-                              cols, ignore_index,
+                              (const float*)gscale, (const float*)upstream,
+                              (void*)dlogits, rows, cols, ignore_index,
+                              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // loss, lse and dlogits = *g0 * (softmax - onehot) from one read of the
+  // logits; cols <= ce_fused_max_cols(dtype).
+  m.def("ce_fused_max_cols", &adapcc::ce_fused_max_cols, py::arg("dtype"));
+  m.def("ce_fwd_grad",
+        [](int dtype, uintptr_t logits, uintptr_t targets, uintptr_t g0,
+           uintptr_t loss, uintptr_t lse, uintptr_t dlogits, long rows,
+           long cols, long ignore_index, uintptr_t stream) {
+          adapcc::ce_forward_grad(dtype, (const void*)logits,
+                                  (const void*)targets, (const float*)g0,
+                                  (float*)loss, (float*)lse, (void*)dlogits,
+                                  rows, cols, ignore_index,
+                                  reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+  // Column sums of up to three [nslots, cols] fp32 partial arrays (0: absent)
+  // into [cols] outputs of out_dtype, in a fixed order.
+  m.def("colsum_fold",
+        [](int out_dtype, uintptr_t a0, uintptr_t a1, uintptr_t a2,
+           uintptr_t o0, uintptr_t o1, uintptr_t o2, long nslots, long cols,
+           uintptr_t stream) {
+          adapcc::colsum_fold(out_dtype, (const float*)a0, (const float*)a1,
+                              (const float*)a2, (void*)o0, (void*)o1,
+                              (void*)o2, nslots, cols,
                               reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
@@ -428,6 +471,21 @@ PYBIND11_MODULE(_core, m) {
           adapcc::gelu_backward(dtype, (const void*)x, (const void*)dy,
                                 (void*)dx, n,
                                 reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        });
+
+  // GeLU backward over [rows, cols] that also leaves fp32 column partials of
+  // the rounded dx, one [cols] row per block, in ws [nblocks, cols].
+  m.def("gelu_bias_supported", &adapcc::gelu_bias_supported, py::arg("cols"),
+        py::arg("dtype"));
+  m.def("gelu_bwd_bias",
+        [](int dtype, uintptr_t x, uintptr_t dy, uintptr_t dx, uintptr_t ws,
+           long rows, long cols, int nblocks, uintptr_t stream) {
+          adapcc::gelu_backward_bias(dtype, (const void*)x, (const void*)dy,
+                                     (void*)dx, (float*)ws, rows, cols,
+                                     nblocks,
+                                     reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         });

@@ -8,7 +8,7 @@
 // use shfl_xor, and the backward fuses dx with per-block dgamma/dbeta
 // partials (single read of dy/x) accumulated in registers — each lane owns
 // a fixed column set — and flushed once per wave; a tiny second kernel
-// folds the per-wave partials.
+// (colsum.hip) folds the per-wave partials.
 //
 // bf16/f16/f32 activations, fp32 statistics; instantiated for the common
 // transformer widths (128..4096, divisible by the 16-byte vector width).
@@ -30,6 +30,7 @@
 
 #include "attn_drop.h"
 #include "common.h"
+#include "ln_cols.h"
 
 #include <stdexcept>
 #include <string>
@@ -391,10 +392,6 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
-
-#define LN_COLS_LIST(X) \
-  X(128) X(256) X(384) X(512) X(640) X(768) X(1024) X(1280) X(1536) \
-  X(2048) X(3072) X(4096)
 
 bool ln_supported_api(long cols, int dtype) {
   const int pv = dtype_size((Dtype)dtype) == 4 ? 4 : 8;

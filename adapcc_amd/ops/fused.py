@@ -7,7 +7,28 @@ way. Its mask is the attention kernels' keep(seed, site, row, col)
 (csrc/attn_drop.h) over the flattened rows, regenerated in the backward and
 never stored; the seed is attention's too: one int64 on the device, drawn
 from torch's generator per call or passed as ``dropout_seed``.
-``dropout_add_keep_mask_reference`` is that mask in torch integer ops."""
+``dropout_add_keep_mask_reference`` is that mask in torch integer ops.
+
+Three fusions drop passes over memory that the training step does not need;
+each has a module-level switch, so one process can run both paths:
+
+``FUSE_CE_GRAD``: when the logits need a gradient, the cross-entropy forward
+keeps each row in registers and writes loss, lse and dlogits (for an
+upstream gradient of 1) after one read (csrc/ce.hip, ``ce_fwd_grad``). The
+backward launches ``ce_bwd`` with the upstream gradient on the device: at
+exactly 1.0 it returns at once and the saved dlogits are the result, any
+other value recomputes them as before. Bits are those of the two-kernel path.
+
+``FUSE_GELU_BIAS_GRAD``: ``fused_gelu(x, bias=b)`` takes the gradient of the
+bias that the linear in front added from the GeLU backward, which sums the dx
+it writes down the columns (csrc/gelu.hip, ``gelu_bwd_bias``): torch's reduce
+kernel over dx goes. ``gelu_bias_grad_fusable`` says when; the caller then
+hands the linear ``b.detach()``.
+
+``FUSE_COLSUM_FOLD``: the per-wave dgamma/dbeta partials of the LayerNorm
+backwards, and the GeLU's, are summed by one ``colsum_fold`` launch
+(csrc/colsum.hip) that writes the parameter dtype, where torch took a reduce
+and a cast kernel per array."""
 
 from __future__ import annotations
 
@@ -18,6 +39,11 @@ import torch.nn as nn
 
 _CORE = None
 _DT = {}
+
+# see the module docstring; tests flip these to compare the paths
+FUSE_CE_GRAD = True
+FUSE_GELU_BIAS_GRAD = True
+FUSE_COLSUM_FOLD = True
 
 
 def _core():
@@ -39,6 +65,22 @@ def ln_fusable(cols: int, dtype: torch.dtype) -> bool:
     if not c or dtype not in _DT:
         return False
     return bool(c.ln_supported(cols, _DT[dtype]))
+
+
+def _fold_partials(parts, nslots: int, cols: int, dtype: torch.dtype):
+    """Column sums of up to three [nslots * cols] fp32 partial arrays, each
+    as a [cols] tensor of dtype: one colsum_fold launch, or torch's reduce
+    and cast per array with the switch off."""
+    if not (FUSE_COLSUM_FOLD and cols % 4 == 0 and dtype in _DT):
+        return [p.view(nslots, cols).sum(0).to(dtype) for p in parts]
+    dev = parts[0].device
+    outs = [torch.empty(cols, dtype=dtype, device=dev) for _ in parts]
+    pad = [0] * (3 - len(parts))
+    _core().colsum_fold(
+        _DT[dtype], *([p.data_ptr() for p in parts] + pad),
+        *([o.data_ptr() for o in outs] + pad), nslots, cols,
+        torch.cuda.current_stream(dev).cuda_stream)
+    return outs
 
 
 class _FusedLayerNormFn(torch.autograd.Function):
@@ -78,20 +120,23 @@ class _FusedLayerNormFn(torch.autograd.Function):
                  weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                  dx.data_ptr(), wsg.data_ptr(), wsb.data_ptr(),
                  rows, cols, nblocks, stream)
-        # fold the per-wave partials (torch's tree reduction is optimal here)
-        dgamma = wsg.view(nslots, cols).sum(0).to(weight.dtype)
-        dbeta = wsb.view(nslots, cols).sum(0).to(weight.dtype)
+        dgamma, dbeta = _fold_partials([wsg, wsb], nslots, cols, weight.dtype)
         return dx, dgamma, dbeta, None
 
 
 class _FusedCrossEntropyFn(torch.autograd.Function):
     """Mean cross-entropy over rows without materializing log-softmax
     (csrc/ce.hip). Saves ~2x the logits tensor of HBM traffic plus the
-    6.6 GB log-softmax intermediate on the GPT-2 flagship path."""
+    6.6 GB log-softmax intermediate on the GPT-2 flagship path.
+
+    First-order only: the backward launches kernels on raw pointers, and on
+    the fused path the gradient it returns is a tensor saved by the forward,
+    which a recompute overwrites in place. Double backward through this
+    Function is not supported."""
 
     @staticmethod
     def forward(ctx, logits: torch.Tensor, targets: torch.Tensor,
-                ignore_index: int) -> torch.Tensor:
+                ignore_index: int, want_grad: bool = False) -> torch.Tensor:
         c = _core()
         lc = logits.contiguous()
         rows, cols = lc.shape
@@ -99,26 +144,49 @@ class _FusedCrossEntropyFn(torch.autograd.Function):
         loss = torch.empty(rows, dtype=torch.float32, device=lc.device)
         lse = torch.empty_like(loss)
         stream = torch.cuda.current_stream(lc.device).cuda_stream
-        c.ce_fwd(_DT[lc.dtype], lc.data_ptr(), tc.data_ptr(),
-                 loss.data_ptr(), lse.data_ptr(), rows, cols, ignore_index,
-                 stream)
         n_valid = (tc != ignore_index).sum().to(torch.float32).clamp(min=1)
-        ctx.save_for_backward(lc, tc, lse, n_valid)
         ctx.ignore_index = ignore_index
+        # training: dlogits leave the forward's one read of the logits
+        # (want_grad: a backward will come; the caller knows, in here grad
+        # mode is off and needs_input_grad ignores no_grad)
+        ctx.fused = bool(FUSE_CE_GRAD and want_grad
+                         and cols <= c.ce_fused_max_cols(_DT[lc.dtype]))
+        if ctx.fused:
+            # the backward's gscale for an upstream gradient of 1
+            g0 = (torch.ones_like(n_valid) / n_valid).reshape(1)
+            dlogits = torch.empty_like(lc)
+            c.ce_fwd_grad(_DT[lc.dtype], lc.data_ptr(), tc.data_ptr(),
+                          g0.data_ptr(), loss.data_ptr(), lse.data_ptr(),
+                          dlogits.data_ptr(), rows, cols, ignore_index, stream)
+            ctx.save_for_backward(lc, tc, lse, n_valid, dlogits)
+            ctx.dlogits_fresh = True
+        else:
+            c.ce_fwd(_DT[lc.dtype], lc.data_ptr(), tc.data_ptr(),
+                     loss.data_ptr(), lse.data_ptr(), rows, cols,
+                     ignore_index, stream)
+            ctx.save_for_backward(lc, tc, lse, n_valid)
         return loss.sum() / n_valid
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         c = _core()
-        logits, targets, lse, n_valid = ctx.saved_tensors
+        logits, targets, lse, n_valid, *saved = ctx.saved_tensors
         rows, cols = logits.shape
-        gscale = (grad_out.to(torch.float32) / n_valid).reshape(1).contiguous()
-        dlogits = torch.empty_like(logits)
+        up = grad_out.to(torch.float32).reshape(1).contiguous()
+        gscale = up / n_valid
+        if ctx.fused and ctx.dlogits_fresh:
+            # the kernel reads the upstream gradient itself (no host sync):
+            # at 1.0 the saved dlogits stand, else it recomputes over them.
+            # Only once: what this returns may end up as a leaf's .grad.
+            ctx.dlogits_fresh = False
+            dlogits, up_ptr = saved[0], up.data_ptr()
+        else:
+            dlogits, up_ptr = torch.empty_like(logits), 0
         stream = torch.cuda.current_stream(logits.device).cuda_stream
         c.ce_bwd(_DT[logits.dtype], logits.data_ptr(), targets.data_ptr(),
-                 lse.data_ptr(), gscale.data_ptr(), dlogits.data_ptr(),
-                 rows, cols, ctx.ignore_index, stream)
-        return dlogits, None, None
+                 lse.data_ptr(), gscale.data_ptr(), up_ptr,
+                 dlogits.data_ptr(), rows, cols, ctx.ignore_index, stream)
+        return dlogits, None, None, None
 
 
 def fused_cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
@@ -134,7 +202,9 @@ def fused_cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
         and logits.dtype in _DT
         and not torch.is_autocast_enabled()
     ):
-        return _FusedCrossEntropyFn.apply(logits, targets, ignore_index)
+        return _FusedCrossEntropyFn.apply(
+            logits, targets, ignore_index,
+            torch.is_grad_enabled() and logits.requires_grad)
     return torch.nn.functional.cross_entropy(
         logits.float(), targets, ignore_index=ignore_index)
 
@@ -167,11 +237,85 @@ class _FusedGeluFn(torch.autograd.Function):
         return dx
 
 
-def fused_gelu(x: torch.Tensor) -> torch.Tensor:
+class _FusedGeluBiasFn(torch.autograd.Function):
+    """_FusedGeluFn over [..., cols] whose backward also returns the column
+    sum of dx as the gradient of ``bias``: the bias a linear added to x,
+    handed to that linear detached."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+        c = _core()
+        xc = x.contiguous()
+        y = torch.empty_like(xc)
+        stream = torch.cuda.current_stream(xc.device).cuda_stream
+        c.gelu_fwd(_DT[xc.dtype], xc.data_ptr(), y.data_ptr(), xc.numel(),
+                   stream)
+        ctx.save_for_backward(xc)
+        ctx.bias_dtype = bias.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        c = _core()
+        (x,) = ctx.saved_tensors
+        cols = x.shape[-1]
+        rows = x.numel() // cols
+        dyc = dy.contiguous()
+        dx = torch.empty_like(x)
+        # one partial row per block: 1024 blocks fill the chip, and the
+        # workspace stays a small fraction of dx
+        nblocks = max(1, min(1024, (rows + 3) // 4))
+        ws = torch.empty(nblocks * cols, dtype=torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        c.gelu_bwd_bias(_DT[x.dtype], x.data_ptr(), dyc.data_ptr(),
+                        dx.data_ptr(), ws.data_ptr(), rows, cols, nblocks,
+                        stream)
+        (dbias,) = _fold_partials([ws], nblocks, cols, ctx.bias_dtype)
+        return dx, dbias
+
+
+def _gelu_kernel_path(device: torch.device, dtype: torch.dtype) -> bool:
+    return bool(device.type == "cuda" and _core() and dtype in _DT
+                and not torch.is_autocast_enabled())
+
+
+def gelu_bias_grad_fusable(device: torch.device, dtype: torch.dtype,
+                           rows: int, cols: int,
+                           bias: Optional[torch.Tensor]) -> bool:
+    """Whether ``fused_gelu(x, bias=bias)`` on an x of this device and dtype
+    with ``rows`` rows of ``cols`` elements takes bias' gradient from the
+    GeLU backward: the kernel path, bf16 at a width it is built for, at
+    least one row, a [cols] bias of a kernel dtype that wants a gradient.
+    The caller asks before the linear and, on True, gives the linear
+    ``bias.detach()``; ``fused_gelu`` decides by this function alone, so the
+    two cannot disagree."""
+    if not (FUSE_GELU_BIAS_GRAD and bias is not None and rows >= 1
+            and cols >= 1 and _gelu_kernel_path(device, dtype)):
+        return False
+    if not (torch.is_grad_enabled() and bias.requires_grad):
+        return False
+    if bias.device != device or bias.dtype not in _DT \
+            or bias.shape != (cols,):
+        return False
+    return bool(_core().gelu_bias_supported(cols, _DT[dtype]))
+
+
+def fused_gelu(x: torch.Tensor,
+               bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.gelu(x, approximate='tanh') drop-in; HIP kernel on GPU, torch
-    fallback elsewhere."""
-    if x.is_cuda and _core() and x.dtype in _DT \
-            and not torch.is_autocast_enabled():
+    fallback elsewhere.
+
+    bias: the bias that the linear which produced x added. Where
+    ``gelu_bias_grad_fusable`` holds for x and bias, the caller has given
+    that linear ``bias.detach()`` and bias gets its gradient here: dx summed
+    over the rows, rounded to bias' dtype. Everywhere else (CPU, autocast,
+    other widths, the switch off) bias is ignored: it stayed attached to the
+    linear and gets its gradient there."""
+    if _gelu_kernel_path(x.device, x.dtype):
+        cols = x.shape[-1] if x.dim() >= 1 else 0
+        if gelu_bias_grad_fusable(x.device, x.dtype,
+                                  x.numel() // max(cols, 1), cols, bias):
+            return _FusedGeluBiasFn.apply(x, bias)
         return _FusedGeluFn.apply(x)
     return torch.nn.functional.gelu(x, approximate="tanh")
 
@@ -316,8 +460,7 @@ class _DropoutAddLayerNormFn(torch.autograd.Function):
         _launch_dropadd_bwd(dyc, dxc, x_new, weight, mean, rstd, dres, dh,
                             wsg, wsb, nblocks, ctx.dropout_p,
                             seed[0] if seed else None, ctx.site)
-        dgamma = wsg.view(nslots, cols).sum(0).to(weight.dtype)
-        dbeta = wsb.view(nslots, cols).sum(0).to(weight.dtype)
+        dgamma, dbeta = _fold_partials([wsg, wsb], nslots, cols, weight.dtype)
         return (dh if dh is not None else dres, dres, dgamma, dbeta,
                 None, None, None, None)
 
