@@ -39,7 +39,9 @@ the call can sit in a captured graph whose ``cu_seqlens`` is refilled
 between replays. The dropout mask of sequence i, head h is plane i * H + h
 of the same function, q and k counted from the sequence start. Off the
 kernel path the same function is composed from torch SDPA under a
-block-diagonal mask.
+block-diagonal mask. To everything between the entry points and the kernels
+this mode is the fixed-length call with B = 1, S = total and the map
+(``tmap``) as one more argument.
 """
 
 from __future__ import annotations
@@ -58,8 +60,22 @@ __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
            "fa_qkv_varlen_supported", "varlen_tile_map_reference"]
 
 
+_QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
+
+
 def _strides3(t: torch.Tensor):
     return [t.stride(0), t.stride(1), t.stride(2)]
+
+
+def _rows4(t: torch.Tensor) -> torch.Tensor:
+    """[total,H,D] -> its [1,H,total,D] view, the kernels' tensor form."""
+    return t.unsqueeze(0).transpose(1, 2)
+
+
+def _bhsd(t: torch.Tensor) -> torch.Tensor:
+    """The kernels' form of either layout: [B,H,S,D] as it is, packed
+    sequences [total,H,D] as their [1,H,total,D] view."""
+    return t if t.dim() == 4 else _rows4(t)
 
 
 def _row_ok(t: torch.Tensor) -> bool:
@@ -98,14 +114,21 @@ def _gqa_shapes_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                if i != heads_at)
 
 
-def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                 causal: bool, dropout_p: float) -> bool:
-    """q [B,H,S,D]; k, v [B,Hk,S,D] of one shape with H % Hk == 0."""
-    if q.dim() != 4 or not _gqa_shapes_ok(q, k, v, 1):
+def _qkv_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dim: int,
+            causal: bool, dropout_p: float) -> bool:
+    """Separate q, k, v of ``dim`` dimensions, heads in dimension 1."""
+    if q.dim() != dim or not _gqa_shapes_ok(q, k, v, 1):
         return False
+    q, k, v = _bhsd(q), _bhsd(k), _bhsd(v)
     if not (_row_ok(q) and _row_ok(k) and _row_ok(v)):
         return False
     return _kernel_ok(q, q.shape[3], q.shape[2], causal, dropout_p)
+
+
+def fa_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                 causal: bool, dropout_p: float) -> bool:
+    """q [B,H,S,D]; k, v [B,Hk,S,D] of one shape with H % Hk == 0."""
+    return _qkv_ok(q, k, v, 4, causal, dropout_p)
 
 
 # ---------------------------------------------------------------------------
@@ -183,24 +206,37 @@ def _seed_tensor(seed: Optional[torch.Tensor],
     return seed.view(1)
 
 
+def _tmap_kw(tmap: Optional[torch.Tensor], total: int):
+    """The bindings' keywords for a tile map; none means fixed length. The
+    map has total // 128 + n_seqs rows, which gives the sequence count."""
+    if tmap is None:
+        return {}
+    return {"tmap": tmap.data_ptr(), "n_seqs": tmap.shape[0] - total // _QT}
+
+
 def _launch_fwd(q, k, v, o, lse, scale, causal=True, dropout_p=0.0,
-                seed=None):
+                seed=None, tmap=None):
+    """q, k, v, o: [B,H,S,D]; lse: [B,H,S] fp32. With ``tmap``, the tile
+    map of ``_varlen_plan``, they hold packed sequences: [1,H,total,D]
+    views and [1,H,total]."""
     B, H, S, _ = q.shape
     strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     _core().fa_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    lse.data_ptr(), B, H, S, strides, scale, stream, causal,
                    dropout_p, seed.data_ptr() if dropout_p > 0.0 else 0,
-                   head_dim=q.shape[3], n_kv_head=k.shape[1])
+                   head_dim=q.shape[3], n_kv_head=k.shape[1],
+                   **_tmap_kw(tmap, S))
 
 
 def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
-                delta=None, dropout_p=0.0, seed=None):
+                delta=None, dropout_p=0.0, seed=None, tmap=None):
     """dq/dk/dv are written in place; delta = rowsum(dO*O) is computed by
     the dq kernel into a workspace (``delta``: contiguous [B,H,S] fp32, made
     here when not given) the dkv kernel then reads. With dropout, ``seed``
     is the forward's seed tensor. k, v, dk, dv may have fewer heads than q
-    (H % Hk == 0); dk, dv are then the sums over each group."""
+    (H % Hk == 0); dk, dv are then the sums over each group. ``tmap`` as in
+    ``_launch_fwd``."""
     B, H, S, _ = q.shape
     # e.g. y.sum().backward() hands down an expanded, zero-stride dout
     do = dout if _row_ok(dout) else dout.contiguous()
@@ -215,25 +251,35 @@ def _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, scale, causal=True,
                    dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S,
                    strides, scale, stream, causal, dropout_p,
                    seed.data_ptr() if dropout_p > 0.0 else 0,
-                   head_dim=q.shape[3], n_kv_head=k.shape[1])
+                   head_dim=q.shape[3], n_kv_head=k.shape[1],
+                   **_tmap_kw(tmap, S))
 
 
-def _fa_forward_lse(q, k, v, scale, causal, dropout_p=0.0, seed=None):
+def _fa_forward_lse(q, k, v, scale, causal, dropout_p=0.0, seed=None,
+                    tmap=None):
     """Forward only: (o, lse), lse the [B,H,S] fp32 natural-log logsumexp
-    of the scaled scores (dropout does not enter it)."""
-    B, H, S, D = q.shape
-    # O lives in [B,S,H,D] memory so the caller's
-    # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
-    o = torch.empty((B, S, H, D), dtype=q.dtype,
-                    device=q.device).transpose(1, 2)
+    of the scaled scores (dropout does not enter it). With ``tmap`` q, k, v
+    hold packed sequences, [total,H,D] or their [1,H,total,D] views, o comes
+    back in q's form and lse is [1,H,total]."""
+    B, H, S, D = _bhsd(q).shape
+    if q.dim() == 4:
+        # O lives in [B,S,H,D] memory so the caller's
+        # transpose(1,2).view(B,T,C) is free; returned as its [B,H,S,D] view
+        o = torch.empty((B, S, H, D), dtype=q.dtype,
+                        device=q.device).transpose(1, 2)
+    else:
+        o = torch.empty((S, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    _launch_fwd(q, k, v, o, lse, scale, causal=causal, dropout_p=dropout_p,
-                seed=seed)
+    _launch_fwd(_bhsd(q), _bhsd(k), _bhsd(v), _bhsd(o), lse, scale,
+                causal=causal, dropout_p=dropout_p, seed=seed, tmap=tmap)
     return o, lse
 
 
 def _heads(t: torch.Tensor, n_head: int) -> torch.Tensor:
-    """[B,T,C] (any row stride) -> its [B,H,T,C/H] view."""
+    """[B,T,C] (any row stride) -> its [B,H,T,C/H] view; packed sequences
+    [total,C] -> [1,H,total,C/H]."""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
     B, T, C = t.shape
     return t.view(B, T, n_head, C // n_head).transpose(1, 2)
 
@@ -254,11 +300,10 @@ def _qkv_parts(t: torch.Tensor, n_head: int, Hk: int):
     return t.split([n_head * D, Hk * D, Hk * D], dim=-1)
 
 
-def _qkv_heads(t: torch.Tensor, n_head: int, Hk: int, heads=None):
+def _qkv_heads(t: torch.Tensor, n_head: int, Hk: int):
     """The three parts of t as [B,H,T,D], [B,Hk,T,D], [B,Hk,T,D] views."""
-    heads = heads or _heads
     q, k, v = _qkv_parts(t, n_head, Hk)
-    return heads(q, n_head), heads(k, Hk), heads(v, Hk)
+    return _heads(q, n_head), _heads(k, Hk), _heads(v, Hk)
 
 
 def _drop_kw(ctx, seed):
@@ -269,70 +314,78 @@ def _drop_kw(ctx, seed):
     return {}
 
 
+def _plan_of(cu_seqlens: Optional[torch.Tensor], total: int):
+    """The tile map of a packed-sequence call; None at fixed length."""
+    return None if cu_seqlens is None else _varlen_plan(cu_seqlens, total)
+
+
 class _FlashAttnFn(torch.autograd.Function):
-    """[B,H,S,D] q, k, v; causal needs S % 128 == 0. seed: the one-element
-    int64 device tensor of the dropout mask, None at dropout_p = 0."""
+    """[B,H,S,D] q, k, v; causal needs S % 128 == 0. With cu_seqlens, the
+    int32 row offsets of sequences held back to back, [total,H,D] q, k, v
+    of any lengths. seed: the one-element int64 device tensor of the
+    dropout mask, None at dropout_p = 0."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, dropout_p=0.0, seed=None):
+    def forward(ctx, q, k, v, scale, causal, dropout_p=0.0, seed=None,
+                cu_seqlens=None):
         ctx.scale, ctx.causal, ctx.dropout_p = scale, causal, dropout_p
-        o, lse = _fa_forward_lse(q, k, v, scale, causal,
+        tmap = _plan_of(cu_seqlens, q.shape[0])
+        o, lse = _fa_forward_lse(q, k, v, scale, causal, tmap=tmap,
                                  **_drop_kw(ctx, seed))
-        if dropout_p > 0.0:
-            ctx.save_for_backward(q, k, v, o, lse, seed)
-        else:
-            ctx.save_for_backward(q, k, v, o, lse)
+        # tmap and seed are None where the mode has none
+        ctx.save_for_backward(q, k, v, o, lse, tmap, seed)
         return o
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o, lse, *seed = ctx.saved_tensors
+        q, k, v, o, lse, tmap, seed = ctx.saved_tensors
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         dk = torch.empty(k.shape, dtype=q.dtype, device=q.device)
         dv = torch.empty_like(dk)
-        _launch_bwd(q, k, v, o, dout, lse, dq, dk, dv, ctx.scale,
-                    causal=ctx.causal,
-                    **_drop_kw(ctx, seed[0] if seed else None))
-        return dq, dk, dv, None, None, None, None
+        _launch_bwd(_bhsd(q), _bhsd(k), _bhsd(v), _bhsd(o), _bhsd(dout), lse,
+                    _bhsd(dq), _bhsd(dk), _bhsd(dv), ctx.scale,
+                    causal=ctx.causal, tmap=tmap, **_drop_kw(ctx, seed))
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _FlashAttnQkvFn(torch.autograd.Function):
     """Attention straight off the packed projection: q, k, v are strided
     views of qkv [B,T,(H+2*Hk)*D] (n_kv_head None: Hk = H, [B,T,3C]), O is
     written as [B,T,H*D], and the backward writes dq, dk, dv into the three
-    parts of one gradient of qkv's shape."""
+    parts of one gradient of qkv's shape. With cu_seqlens, qkv is
+    [total,(H+2*Hk)*D] and O [total,H*D], sequences back to back."""
 
     @staticmethod
     def forward(ctx, qkv, n_head, scale, causal, dropout_p=0.0, seed=None,
-                n_kv_head=None):
-        B, T, C3 = qkv.shape
+                n_kv_head=None, cu_seqlens=None):
         Hk = n_head if n_kv_head is None else n_kv_head
-        C = C3 // (n_head + 2 * Hk) * n_head
+        C = qkv.shape[-1] // (n_head + 2 * Hk) * n_head
         q, k, v = _qkv_heads(qkv, n_head, Hk)
-        y = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
+        B, _, T, _ = q.shape
+        tmap = _plan_of(cu_seqlens, T)
+        y = torch.empty((*qkv.shape[:-1], C), dtype=qkv.dtype,
+                        device=qkv.device)
         lse = torch.empty((B, n_head, T), dtype=torch.float32,
                           device=qkv.device)
         ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
         ctx.dropout_p, ctx.n_kv_head = dropout_p, Hk
         _launch_fwd(q, k, v, _heads(y, n_head), lse, scale, causal=causal,
-                    **_drop_kw(ctx, seed))
-        if dropout_p > 0.0:
-            ctx.save_for_backward(qkv, y, lse, seed)
-        else:
-            ctx.save_for_backward(qkv, y, lse)
+                    tmap=tmap, **_drop_kw(ctx, seed))
+        # tmap and seed are None where the mode has none
+        ctx.save_for_backward(qkv, y, lse, tmap, seed)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        qkv, y, lse, *seed = ctx.saved_tensors
+        qkv, y, lse, tmap, seed = ctx.saved_tensors
         H = ctx.n_head
         q, k, v = _qkv_heads(qkv, H, ctx.n_kv_head)
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = _qkv_heads(dqkv, H, ctx.n_kv_head)
         _launch_bwd(q, k, v, _heads(y, H), _heads(dy, H), lse, dq, dk, dv,
-                    ctx.scale, causal=ctx.causal,
-                    **_drop_kw(ctx, seed[0] if seed else None))
-        return dqkv, None, None, None, None, None, None
+                    ctx.scale, causal=ctx.causal, tmap=tmap,
+                    **_drop_kw(ctx, seed))
+        return dqkv, None, None, None, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -352,20 +405,19 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         seed = (_seed_tensor(dropout_seed, q.device) if dropout_p > 0.0
                 else None)
         return _FlashAttnFn.apply(q, k, v, s, causal, dropout_p, seed)
+    gqa = False
     if q.dim() == 4 and k.dim() == 4 and v.dim() == 4:
         H, Hk = q.shape[1], k.shape[1]
         if v.shape[1] != Hk:
             raise ValueError("flash_attention: k and v must have one head "
                              f"count, got {Hk} and {v.shape[1]}")
-        if Hk != H:
-            if Hk < 1 or H % Hk != 0:
-                raise ValueError("flash_attention: the K/V head count must "
-                                 f"divide q's, got {H} and {Hk}")
-            return torch.nn.functional.scaled_dot_product_attention(
-                q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale,
-                enable_gqa=True)
+        if Hk != H and (Hk < 1 or H % Hk != 0):
+            raise ValueError("flash_attention: the K/V head count must "
+                             f"divide q's, got {H} and {Hk}")
+        gqa = Hk != H
     return torch.nn.functional.scaled_dot_product_attention(
-        q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale)
+        q, k, v, is_causal=causal, dropout_p=dropout_p, scale=scale,
+        enable_gqa=gqa)
 
 
 def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
@@ -383,25 +435,26 @@ def _attention_qkv_composed(qkv: torch.Tensor, n_head: int,
     return y.transpose(1, 2).contiguous().view(B, T, n_head * q.shape[3])
 
 
-def _qkv_width(n_head: int, n_kv_head: Optional[int]) -> int:
-    """Heads across a packed projection's row, H + 2*Hk; 0 when n_kv_head
-    does not divide n_head."""
-    Hk = n_head if n_kv_head is None else n_kv_head
-    if n_head < 1 or Hk < 1 or n_head % Hk != 0:
-        return 0
-    return n_head + 2 * Hk
+def _packed_ok(qkv: torch.Tensor, dim: int, n_head: int,
+               n_kv_head: Optional[int], causal: bool,
+               dropout_p: float) -> bool:
+    """A packed projection [.., S, (H + 2*Hk)*D] of ``dim`` dimensions."""
+    try:
+        W = n_head + 2 * _kv_heads("", n_head, n_kv_head)
+    except ValueError:
+        return False
+    if qkv.dim() != dim or qkv.shape[0] < 1 or qkv.shape[-1] % W:
+        return False
+    if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
+        return False
+    return _kernel_ok(qkv, qkv.shape[-1] // W, qkv.shape[-2], causal,
+                      dropout_p)
 
 
 def fa_qkv_supported(qkv: torch.Tensor, n_head: int,
                      dropout_p: float, causal: bool = True,
                      n_kv_head: Optional[int] = None) -> bool:
-    W = _qkv_width(n_head, n_kv_head)
-    if not W or qkv.dim() != 3 or qkv.shape[0] < 1 or qkv.shape[2] % W:
-        return False
-    if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
-        return False
-    return _kernel_ok(qkv, qkv.shape[2] // W, qkv.shape[1], causal,
-                      dropout_p)
+    return _packed_ok(qkv, 3, n_head, n_kv_head, causal, dropout_p)
 
 
 def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
@@ -433,9 +486,6 @@ def flash_attention_qkv(qkv: torch.Tensor, n_head: int,
 # ---------------------------------------------------------------------------
 # Variable-length (packed sequences) attention
 # ---------------------------------------------------------------------------
-_QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
-
-
 def _check_cu_seqlens(name: str, cu_seqlens, device: torch.device) -> None:
     """Shape, dtype and device of cu_seqlens; its contents are never read
     on the host."""
@@ -461,43 +511,21 @@ def _cu_ok(cu_seqlens, device: torch.device) -> bool:
     return cu_seqlens.is_contiguous() and cu_seqlens.data_ptr() % 4 == 0
 
 
-def _rows4(t: torch.Tensor) -> torch.Tensor:
-    """[total,H,D] -> its [1,H,total,D] view, the kernels' tensor form."""
-    return t.unsqueeze(0).transpose(1, 2)
-
-
-def _varlen_kernel_ok(t: torch.Tensor, D: int, total: int,
-                      dropout_p: float) -> bool:
-    """_kernel_ok without a length condition: any total >= 1."""
-    return _kernel_ok(t, D, total, False, dropout_p)
-
-
 def fa_varlen_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                         cu_seqlens: torch.Tensor, causal: bool,
                         dropout_p: float) -> bool:
-    """q [total,H,D]; k, v [total,Hk,D] of one shape with H % Hk == 0."""
-    if q.dim() != 3 or not _gqa_shapes_ok(q, k, v, 1):
-        return False
-    if not _cu_ok(cu_seqlens, q.device):
-        return False
-    if not all(_row_ok(_rows4(t)) for t in (q, k, v)):
-        return False
-    return _varlen_kernel_ok(q, q.shape[2], q.shape[0], dropout_p)
+    """q [total,H,D]; k, v [total,Hk,D] of one shape with H % Hk == 0. No
+    length condition, causal or not: any total >= 1."""
+    return (_cu_ok(cu_seqlens, q.device)
+            and _qkv_ok(q, k, v, 3, False, dropout_p))
 
 
 def fa_qkv_varlen_supported(qkv: torch.Tensor, n_head: int,
                             cu_seqlens: torch.Tensor, dropout_p: float,
                             causal: bool = True,
                             n_kv_head: Optional[int] = None) -> bool:
-    W = _qkv_width(n_head, n_kv_head)
-    if not W or qkv.dim() != 2 or qkv.shape[1] % W:
-        return False
-    if not _cu_ok(cu_seqlens, qkv.device):
-        return False
-    if not qkv.is_contiguous() or qkv.data_ptr() % 16 != 0:
-        return False
-    return _varlen_kernel_ok(qkv, qkv.shape[1] // W, qkv.shape[0],
-                             dropout_p)
+    return (_cu_ok(cu_seqlens, qkv.device)
+            and _packed_ok(qkv, 2, n_head, n_kv_head, False, dropout_p))
 
 
 def varlen_tile_map_reference(cu_seqlens, total: int) -> torch.Tensor:
@@ -545,132 +573,6 @@ def _varlen_plan(cu_seqlens: torch.Tensor, total: int) -> torch.Tensor:
     return tmap
 
 
-def _launch_varlen_fwd(q, k, v, o, lse, tmap, n_seqs, scale, causal=True,
-                       dropout_p=0.0, seed=None):
-    """q, k, v, o: [1,H,total,D] views; lse: [H,total] fp32."""
-    _, H, total, _ = q.shape
-    strides = _strides3(q) + _strides3(k) + _strides3(v) + _strides3(o)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    _core().fa_varlen_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          o.data_ptr(), lse.data_ptr(), tmap.data_ptr(),
-                          total, n_seqs, H, strides, scale, stream, causal,
-                          dropout_p,
-                          seed.data_ptr() if dropout_p > 0.0 else 0,
-                          head_dim=q.shape[3], n_kv_head=k.shape[1])
-
-
-def _launch_varlen_bwd(q, k, v, o, dout, lse, dq, dk, dv, tmap, n_seqs,
-                       scale, causal=True, delta=None, dropout_p=0.0,
-                       seed=None):
-    """As _launch_bwd on [1,H,total,D] views; the delta workspace is
-    contiguous [H,total] fp32."""
-    _, H, total, _ = q.shape
-    do = dout if _row_ok(dout) else dout.contiguous()
-    if delta is None:
-        delta = torch.empty((H, total), dtype=torch.float32,
-                            device=q.device)
-    strides = (_strides3(q) + _strides3(k) + _strides3(v) + _strides3(o) +
-               _strides3(do) + _strides3(dq) + _strides3(dk) +
-               _strides3(dv))
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    _core().fa_varlen_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-                          delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                          dv.data_ptr(), tmap.data_ptr(), total, n_seqs, H,
-                          strides, scale, stream, causal, dropout_p,
-                          seed.data_ptr() if dropout_p > 0.0 else 0,
-                          head_dim=q.shape[3], n_kv_head=k.shape[1])
-
-
-def _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale, causal,
-                           dropout_p=0.0, seed=None):
-    """Forward only: (o [total,H,D], lse [H,total] fp32, tile map)."""
-    total, H, D = q.shape
-    tmap = _varlen_plan(cu_seqlens, total)
-    o = torch.empty((total, H, D), dtype=q.dtype, device=q.device)
-    lse = torch.empty((H, total), dtype=torch.float32, device=q.device)
-    _launch_varlen_fwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o), lse, tmap,
-                       cu_seqlens.numel() - 1, scale, causal=causal,
-                       dropout_p=dropout_p, seed=seed)
-    return o, lse, tmap
-
-
-class _FlashAttnVarlenFn(torch.autograd.Function):
-    """[total,H,D] q, k, v that hold sequences back to back, cu_seqlens
-    their int32 row offsets. seed as in _FlashAttnFn."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, scale, causal, dropout_p=0.0,
-                seed=None):
-        ctx.scale, ctx.causal, ctx.dropout_p = scale, causal, dropout_p
-        o, lse, tmap = _fa_varlen_forward_lse(q, k, v, cu_seqlens, scale,
-                                              causal, **_drop_kw(ctx, seed))
-        if dropout_p > 0.0:
-            ctx.save_for_backward(q, k, v, o, lse, tmap, cu_seqlens, seed)
-        else:
-            ctx.save_for_backward(q, k, v, o, lse, tmap, cu_seqlens)
-        return o
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, o, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
-        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty(k.shape, dtype=q.dtype, device=q.device)
-        dv = torch.empty_like(dk)
-        _launch_varlen_bwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o),
-                           _rows4(dout), lse, _rows4(dq), _rows4(dk),
-                           _rows4(dv), tmap, cu_seqlens.numel() - 1,
-                           ctx.scale, causal=ctx.causal,
-                           **_drop_kw(ctx, seed[0] if seed else None))
-        return dq, dk, dv, None, None, None, None, None
-
-
-def _heads2(t: torch.Tensor, n_head: int) -> torch.Tensor:
-    """[total,C] (any row stride) -> its [1,H,total,C/H] view."""
-    return _heads(t.unsqueeze(0), n_head)
-
-
-class _FlashAttnQkvVarlenFn(torch.autograd.Function):
-    """_FlashAttnQkvFn for packed sequences: q, k, v are strided views of
-    qkv [total,(H+2*Hk)*D], O is written as [total,H*D], and the backward
-    writes dq, dk, dv into the three parts of one gradient of qkv's shape."""
-
-    @staticmethod
-    def forward(ctx, qkv, n_head, cu_seqlens, scale, causal, dropout_p=0.0,
-                seed=None, n_kv_head=None):
-        total, C3 = qkv.shape
-        Hk = n_head if n_kv_head is None else n_kv_head
-        C = C3 // (n_head + 2 * Hk) * n_head
-        q, k, v = _qkv_heads(qkv, n_head, Hk, _heads2)
-        tmap = _varlen_plan(cu_seqlens, total)
-        y = torch.empty((total, C), dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty((n_head, total), dtype=torch.float32,
-                          device=qkv.device)
-        ctx.n_head, ctx.scale, ctx.causal = n_head, scale, causal
-        ctx.dropout_p, ctx.n_kv_head = dropout_p, Hk
-        _launch_varlen_fwd(q, k, v, _heads2(y, n_head), lse, tmap,
-                           cu_seqlens.numel() - 1, scale, causal=causal,
-                           **_drop_kw(ctx, seed))
-        if dropout_p > 0.0:
-            ctx.save_for_backward(qkv, y, lse, tmap, cu_seqlens, seed)
-        else:
-            ctx.save_for_backward(qkv, y, lse, tmap, cu_seqlens)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        qkv, y, lse, tmap, cu_seqlens, *seed = ctx.saved_tensors
-        H = ctx.n_head
-        q, k, v = _qkv_heads(qkv, H, ctx.n_kv_head, _heads2)
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = _qkv_heads(dqkv, H, ctx.n_kv_head, _heads2)
-        _launch_varlen_bwd(q, k, v, _heads2(y, H), _heads2(dy, H), lse, dq,
-                           dk, dv, tmap, cu_seqlens.numel() - 1, ctx.scale,
-                           causal=ctx.causal,
-                           **_drop_kw(ctx, seed[0] if seed else None))
-        return dqkv, None, None, None, None, None, None, None
-
-
 def _varlen_mask(cu_seqlens: torch.Tensor, total: int,
                  causal: bool) -> torch.Tensor:
     """[total,total] bool, True where q row (dim 0) may see k row (dim 1):
@@ -716,8 +618,8 @@ def flash_attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         seed = (_seed_tensor(dropout_seed, q.device) if dropout_p > 0.0
                 else None)
-        return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens, s, causal,
-                                        dropout_p, seed)
+        return _FlashAttnFn.apply(q, k, v, s, causal, dropout_p, seed,
+                                  cu_seqlens)
     mask = _varlen_mask(cu_seqlens, q.shape[0], causal)
     gqa = {"enable_gqa": True} if k.shape[1] != q.shape[1] else {}
     y = torch.nn.functional.scaled_dot_product_attention(
@@ -753,8 +655,8 @@ def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
         scale = 1.0 / math.sqrt(D)
         seed = (_seed_tensor(dropout_seed, qkv.device) if dropout_p > 0.0
                 else None)
-        return _FlashAttnQkvVarlenFn.apply(qkv, n_head, cu_seqlens, scale,
-                                           causal, dropout_p, seed, Hk)
+        return _FlashAttnQkvFn.apply(qkv, n_head, scale, causal, dropout_p,
+                                     seed, Hk, cu_seqlens)
     q, k, v = (t.view(total, -1, D) for t in _qkv_parts(qkv, n_head, Hk))
     y = flash_attention_varlen(q, k, v, cu_seqlens, causal=causal,
                                dropout_p=dropout_p,

@@ -1345,6 +1345,23 @@ void check_varlen(const char* name, int total, int n_seqs, int H) {
 // Entries of the tile map, and workgroups in x of a variable-length launch.
 int varlen_max_tiles(int total, int n_seqs) { return total / kQT + n_seqs; }
 
+// Checks the lengths of a launch in either mode and returns the grid of the
+// q-tile kernels, query heads in y. With a tile map S is `total` and there is
+// one batch.
+dim3 q_grid(const char* name, int B, int H, int S, bool causal,
+            const int* tmap, int n_seqs) {
+  if (tmap == nullptr) {
+    check_len(name, S, causal);
+    return dim3((S + kQT - 1) / kQT, B * H);
+  }
+  if (B != 1)
+    throw std::runtime_error(std::string(name) +
+                             ": a tile map needs B == 1, got " +
+                             std::to_string(B));
+  check_varlen(name, S, n_seqs, H);
+  return dim3(varlen_max_tiles(S, n_seqs), H);
+}
+
 // Calls f(kCausal, kRagged, kDrop, kVarlen) with the mode as four
 // std::bool_constant values. The variable-length mode is always ragged, and
 // S means nothing to it.
@@ -1411,10 +1428,13 @@ void bwd_params(FaParams& p, const void* do_, float* delta, void* dq,
   p.dvs = stride_at(strides, 7);
 }
 
-void set_varlen(FaParams& p, const int* tmap, int total) {
-  if (tmap == nullptr) throw std::runtime_error("fa_varlen: no tile map");
+// With a tile map the launch is variable-length: the kernels take every
+// length from the map, so S moves to total and p.S is 0.
+void set_varlen(FaParams& p, const int* tmap) {
+  if (tmap == nullptr) return;
   p.tmap = reinterpret_cast<const int4*>(tmap);
-  p.total = total;
+  p.total = p.S;
+  p.S = 0;
 }
 
 // Calls f(kHD) with the head dimension as a std::integral_constant.
@@ -1490,46 +1510,53 @@ unsigned fa_drop_threshold(double p) { return drop_threshold(p); }
 // memory) when the kernel runs. n_kv_head is the number of heads of k, v
 // (and dk, dv); 0 means H. It must divide H, and query head h then reads
 // K/V head h / (H / n_kv_head).
+//
+// tmap == nullptr is the fixed-length mode: tensors [B, H, S, head_dim], lse
+// and delta fp32 [B, H, S]. With a tile map the same call is the
+// variable-length mode: B must be 1 and S is `total`, the rows of the
+// [total, H, head_dim] tensors handed over as [1, H, total, head_dim] views
+// (batch stride unused), lse and delta fp32 [H, total], and tmap the int32
+// [total/128 + n_seqs, 4] map that fa_varlen_plan filled on the same stream.
+// Nothing here reads cu_seqlens or the map on the host.
 // ---------------------------------------------------------------------------
 void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
                 double dropout_p, const long* seed, int head_dim,
-                int n_kv_head) {
-  check_len("fa_forward", S, causal);
+                int n_kv_head, const int* tmap, int n_seqs) {
+  const dim3 grid = q_grid("fa_forward", B, H, S, causal, tmap, n_seqs);
   check_drop("fa_forward", dropout_p, seed);
   FaParams p = fwd_params("fa_forward", q, k, v, o, lse, H, n_kv_head, S,
                           strides, scale);
   set_drop(p, dropout_p, seed);
-  const dim3 grid((S + kQT - 1) / kQT, B * H);
-  launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, false, stream);
+  set_varlen(p, tmap);
+  launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, tmap != nullptr,
+             stream);
 }
 
-// strides: q, k, v, o, dO, dq, dk, dv. delta is a [B,H,S] f32 workspace the
-// dq kernel fills and the dkv kernel consumes; o and lse are only read.
+// strides: q, k, v, o, dO, dq, dk, dv. delta is an f32 workspace of lse's
+// shape the dq kernel fills and the dkv kernel consumes; o and lse are only
+// read.
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
                  double dropout_p, const long* seed, int head_dim,
-                 int n_kv_head) {
-  check_len("fa_backward", S, causal);
+                 int n_kv_head, const int* tmap, int n_seqs) {
+  const dim3 grid = q_grid("fa_backward", B, H, S, causal, tmap, n_seqs);
   check_drop("fa_backward", dropout_p, seed);
   FaParams p = fwd_params("fa_backward", q, k, v, const_cast<void*>(o),
                           const_cast<float*>(lse), H, n_kv_head, S, strides,
                           scale);
   set_drop(p, dropout_p, seed);
+  set_varlen(p, tmap);
   bwd_params(p, do_, delta, dq, dk, dv, strides);
-  const dim3 grid((S + kQT - 1) / kQT, B * H);
-  launch_bwd(p, grid, head_dim, causal, dropout_p > 0.0, false, stream);
+  launch_bwd(p, grid, head_dim, causal, dropout_p > 0.0, tmap != nullptr,
+             stream);
 }
 
-// ---------------------------------------------------------------------------
-// Variable-length launchers. Tensors are [total, H, head_dim] views (strides
-// as above with the batch stride unused), lse and delta fp32 [H, total], tmap
-// the int32 [total/128 + n_seqs, 4] map that fa_varlen_plan filled on the
-// same stream. Nothing here reads cu_seqlens or the map on the host.
-// ---------------------------------------------------------------------------
+// cu_seqlens: int32 [n_seqs + 1] on the device; fills the tile map that the
+// variable-length launches after it on this stream read.
 void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
                     hipStream_t stream) {
   check_varlen("fa_varlen_plan", total, n_seqs, 1);
@@ -1539,40 +1566,6 @@ void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
                      cu_seqlens, n_seqs, total,
                      varlen_max_tiles(total, n_seqs),
                      reinterpret_cast<int4*>(tmap));
-}
-
-void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
-                       float* lse, const int* tmap, int total, int n_seqs,
-                       int H, const long* strides, float scale,
-                       hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed, int head_dim, int n_kv_head) {
-  check_varlen("fa_varlen_forward", total, n_seqs, H);
-  check_drop("fa_varlen_forward", dropout_p, seed);
-  FaParams p = fwd_params("fa_varlen_forward", q, k, v, o, lse, H, n_kv_head,
-                          0, strides, scale);
-  set_drop(p, dropout_p, seed);
-  set_varlen(p, tmap, total);
-  const dim3 grid(varlen_max_tiles(total, n_seqs), H);
-  launch_fwd(p, grid, head_dim, causal, dropout_p > 0.0, true, stream);
-}
-
-void fa_varlen_backward(const void* q, const void* k, const void* v,
-                        const void* o, const void* do_, const float* lse,
-                        float* delta, void* dq, void* dk, void* dv,
-                        const int* tmap, int total, int n_seqs, int H,
-                        const long* strides, float scale, hipStream_t stream,
-                        bool causal, double dropout_p, const long* seed,
-                        int head_dim, int n_kv_head) {
-  check_varlen("fa_varlen_backward", total, n_seqs, H);
-  check_drop("fa_varlen_backward", dropout_p, seed);
-  FaParams p = fwd_params("fa_varlen_backward", q, k, v,
-                          const_cast<void*>(o), const_cast<float*>(lse), H,
-                          n_kv_head, 0, strides, scale);
-  set_drop(p, dropout_p, seed);
-  set_varlen(p, tmap, total);
-  bwd_params(p, do_, delta, dq, dk, dv, strides);
-  const dim3 grid(varlen_max_tiles(total, n_seqs), H);
-  launch_bwd(p, grid, head_dim, causal, dropout_p > 0.0, true, stream);
 }
 
 // out: [B,H,S,S] bytes, 1 where the element is kept.

@@ -111,29 +111,17 @@ void fa_forward(const void* q, const void* k, const void* v, void* o,
                 float* lse, int B, int H, int S, const long* strides,
                 float scale, hipStream_t stream, bool causal,
                 double dropout_p, const long* seed, int head_dim,
-                int n_kv_head);
+                int n_kv_head, const int* tmap, int n_seqs);
 void fa_backward(const void* q, const void* k, const void* v, const void* o,
                  const void* do_, const float* lse, float* delta, void* dq,
                  void* dk, void* dv, int B, int H, int S, const long* strides,
                  float scale, hipStream_t stream, bool causal,
                  double dropout_p, const long* seed, int head_dim,
-                 int n_kv_head);
+                 int n_kv_head, const int* tmap, int n_seqs);
 void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
                      double dropout_p, hipStream_t stream);
 void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
                     hipStream_t stream);
-void fa_varlen_forward(const void* q, const void* k, const void* v, void* o,
-                       float* lse, const int* tmap, int total, int n_seqs,
-                       int H, const long* strides, float scale,
-                       hipStream_t stream, bool causal, double dropout_p,
-                       const long* seed, int head_dim, int n_kv_head);
-void fa_varlen_backward(const void* q, const void* k, const void* v,
-                        const void* o, const void* do_, const float* lse,
-                        float* delta, void* dq, void* dk, void* dv,
-                        const int* tmap, int total, int n_seqs, int H,
-                        const long* strides, float scale, hipStream_t stream,
-                        bool causal, double dropout_p, const long* seed,
-                        int head_dim, int n_kv_head);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -329,14 +317,14 @@ PYBIND11_MODULE(_core, m) {
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
            int B, int H, int S, const std::vector<long>& strides, float scale,
            uintptr_t stream, bool causal, double dropout_p, uintptr_t seed,
-           int head_dim, int n_kv_head) {
+           int head_dim, int n_kv_head, uintptr_t tmap, int n_seqs) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_fwd: need 12 strides");
           adapcc::fa_forward((const void*)q, (const void*)k, (const void*)v,
                              (void*)o, (float*)lse, B, H, S, strides.data(),
                              scale, reinterpret_cast<hipStream_t>(stream),
                              causal, dropout_p, (const long*)seed, head_dim,
-                             n_kv_head);
+                             n_kv_head, (const int*)tmap, n_seqs);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -344,18 +332,24 @@ PYBIND11_MODULE(_core, m) {
         // dropout_p > 0: seed is the address of one int64 in device memory
         // head_dim: 64 or 128, the width of a q/k/v/o row
         // n_kv_head: heads of k and v (grouped-query attention), 0 = H
+        // tmap != 0: variable-length (packed sequences) attention over
+        // n_seqs sequences. tmap is the map fa_varlen_plan filled, B is 1,
+        // S the total row count, q, k, v, o [1, H, total, head_dim] views
+        // (batch stride unused) and lse fp32 [H, total]
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("B"), py::arg("H"), py::arg("S"),
         py::arg("strides"), py::arg("scale"), py::arg("stream"),
         py::arg("causal") = true, py::arg("dropout_p") = 0.0,
         py::arg("seed") = 0, py::arg("head_dim") = 64,
-        py::arg("n_kv_head") = 0);
+        py::arg("n_kv_head") = 0, py::arg("tmap") = 0,
+        py::arg("n_seqs") = 0);
   m.def("fa_bwd",
         [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
            uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
            uintptr_t dv, int B, int H, int S, const std::vector<long>& strides,
            float scale, uintptr_t stream, bool causal, double dropout_p,
-           uintptr_t seed, int head_dim, int n_kv_head) {
+           uintptr_t seed, int head_dim, int n_kv_head, uintptr_t tmap,
+           int n_seqs) {
           if (strides.size() != 24)
             throw std::runtime_error("fa_bwd: need 24 strides");
           adapcc::fa_backward((const void*)q, (const void*)k, (const void*)v,
@@ -364,7 +358,7 @@ PYBIND11_MODULE(_core, m) {
                               (void*)dk, (void*)dv, B, H, S, strides.data(),
                               scale, reinterpret_cast<hipStream_t>(stream),
                               causal, dropout_p, (const long*)seed, head_dim,
-                              n_kv_head);
+                              n_kv_head, (const int*)tmap, n_seqs);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
         },
@@ -374,7 +368,8 @@ PYBIND11_MODULE(_core, m) {
         py::arg("S"), py::arg("strides"), py::arg("scale"),
         py::arg("stream"), py::arg("causal") = true,
         py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("head_dim") = 64, py::arg("n_kv_head") = 0);
+        py::arg("head_dim") = 64, py::arg("n_kv_head") = 0,
+        py::arg("tmap") = 0, py::arg("n_seqs") = 0);
   // out: [B,H,S,S] uint8, 1 where the attention kernels keep the element
   m.def("fa_dropout_mask",
         [](uintptr_t out, uintptr_t seed, int B, int H, int S,
@@ -389,7 +384,7 @@ PYBIND11_MODULE(_core, m) {
         py::arg("S"), py::arg("dropout_p"), py::arg("stream"));
   // Variable-length (packed sequences) attention. cu_seqlens: int32
   // [n_seqs + 1] on the device; tmap: int32 [total / 128 + n_seqs, 4],
-  // filled by fa_varlen_plan and read by the two launches after it.
+  // filled here and read by the fa_fwd / fa_bwd launches given it.
   m.def("fa_varlen_plan",
         [](uintptr_t cu_seqlens, int n_seqs, int total, uintptr_t tmap,
            uintptr_t stream) {
@@ -401,55 +396,6 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("cu_seqlens"), py::arg("n_seqs"), py::arg("total"),
         py::arg("tmap"), py::arg("stream"));
-  // q, k, v, o: [total, H, head_dim] views, strides as in fa_fwd (batch stride
-  // unused); lse: fp32 [H, total]
-  m.def("fa_varlen_fwd",
-        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t lse,
-           uintptr_t tmap, int total, int n_seqs, int H,
-           const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed, int head_dim,
-           int n_kv_head) {
-          if (strides.size() != 12)
-            throw std::runtime_error("fa_varlen_fwd: need 12 strides");
-          adapcc::fa_varlen_forward(
-              (const void*)q, (const void*)k, (const void*)v, (void*)o,
-              (float*)lse, (const int*)tmap, total, n_seqs, H, strides.data(),
-              scale, reinterpret_cast<hipStream_t>(stream), causal, dropout_p,
-              (const long*)seed, head_dim, n_kv_head);
-          hipError_t e = hipGetLastError();
-          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
-        },
-        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
-        py::arg("lse"), py::arg("tmap"), py::arg("total"), py::arg("n_seqs"),
-        py::arg("H"), py::arg("strides"), py::arg("scale"), py::arg("stream"),
-        py::arg("causal") = true, py::arg("dropout_p") = 0.0,
-        py::arg("seed") = 0, py::arg("head_dim") = 64,
-        py::arg("n_kv_head") = 0);
-  m.def("fa_varlen_bwd",
-        [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t o, uintptr_t dout,
-           uintptr_t lse, uintptr_t delta, uintptr_t dq, uintptr_t dk,
-           uintptr_t dv, uintptr_t tmap, int total, int n_seqs, int H,
-           const std::vector<long>& strides, float scale, uintptr_t stream,
-           bool causal, double dropout_p, uintptr_t seed, int head_dim,
-           int n_kv_head) {
-          if (strides.size() != 24)
-            throw std::runtime_error("fa_varlen_bwd: need 24 strides");
-          adapcc::fa_varlen_backward(
-              (const void*)q, (const void*)k, (const void*)v, (const void*)o,
-              (const void*)dout, (const float*)lse, (float*)delta, (void*)dq,
-              (void*)dk, (void*)dv, (const int*)tmap, total, n_seqs, H,
-              strides.data(), scale, reinterpret_cast<hipStream_t>(stream),
-              causal, dropout_p, (const long*)seed, head_dim, n_kv_head);
-          hipError_t e = hipGetLastError();
-          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
-        },
-        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
-        py::arg("dout"), py::arg("lse"), py::arg("delta"), py::arg("dq"),
-        py::arg("dk"), py::arg("dv"), py::arg("tmap"), py::arg("total"),
-        py::arg("n_seqs"), py::arg("H"), py::arg("strides"),
-        py::arg("scale"), py::arg("stream"), py::arg("causal") = true,
-        py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("head_dim") = 64, py::arg("n_kv_head") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

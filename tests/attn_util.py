@@ -1,5 +1,5 @@
-"""Shared by the flash-attention GPU tests: the fp32 reference and the
-[B,T,C] <-> [B,H,T,C/H] head views."""
+"""Shared by the flash-attention GPU tests: the fp32 reference, the
+[B,T,C] <-> [B,H,T,C/H] head views and the recorder of kernel launches."""
 
 import torch
 
@@ -24,3 +24,29 @@ def heads(t, H):
 def unheads(t):
     B, H, T, d = t.shape
     return t.transpose(1, 2).reshape(B, T, H * d)
+
+
+def record_launches(monkeypatch, extra=None):
+    """Wraps the launch helpers of adapcc_amd.ops.attention for the test and
+    returns the list that collects one (direction, causal, dropout_p,
+    varlen) per launch, varlen saying whether a tile map was passed.
+    ``extra(*args)``, given the helper's positional arguments, returns a
+    tuple that is appended to the entry."""
+    from adapcc_amd.ops import attention
+
+    calls = []
+
+    def wrap(direction, real):
+        def launch(*a, **kw):
+            calls.append((direction, kw.get("causal", True),
+                          kw.get("dropout_p", 0.0),
+                          kw.get("tmap") is not None)
+                         + (extra(*a) if extra else ()))
+            return real(*a, **kw)
+        return launch
+
+    monkeypatch.setattr(attention, "_launch_fwd",
+                        wrap("fwd", attention._launch_fwd))
+    monkeypatch.setattr(attention, "_launch_bwd",
+                        wrap("bwd", attention._launch_bwd))
+    return calls

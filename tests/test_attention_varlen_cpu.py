@@ -254,3 +254,17 @@ def test_gpt2_without_cu_seqlens_is_unchanged(tiny):
             x = x + block.mlp(block.ln_2(x))
         want = model.lm_head(model.ln_f(x))
     torch.testing.assert_close(got, want, rtol=0, atol=0)
+
+
+@pytest.mark.parametrize("name,n_ptrs,n_strides", [("fa_fwd", 5, 12),
+                                                   ("fa_bwd", 10, 24)])
+def test_tile_map_needs_one_batch(name, n_ptrs, n_strides):
+    """The variable-length mode of the launchers is B = 1, S = total: a
+    tile map with B = 2 is refused on the host, before any launch, so the
+    pointers are never followed."""
+    core = pytest.importorskip("adapcc_amd._core")
+    ptr = 4096
+    B, S = 2, 256
+    with pytest.raises(RuntimeError, match="tile map needs B == 1"):
+        getattr(core, name)(*[ptr] * n_ptrs, B, H, S, [64] * n_strides,
+                            SCALE, 0, True, tmap=ptr, n_seqs=2)

@@ -14,7 +14,7 @@ import math
 import pytest
 import torch
 
-from attn_util import ref_attention_f32
+from attn_util import record_launches, ref_attention_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -248,27 +248,6 @@ def test_graph_capture_redraws_seed():
     assert seeds[0] != seeds[1]
 
 
-def _record_launches(monkeypatch):
-    from adapcc_amd.ops import attention
-
-    calls = []
-    real_fwd, real_bwd = attention._launch_fwd, attention._launch_bwd
-
-    def fwd(*a, **kw):
-        calls.append(("fwd", kw.get("causal", True),
-                      kw.get("dropout_p", 0.0)))
-        return real_fwd(*a, **kw)
-
-    def bwd(*a, **kw):
-        calls.append(("bwd", kw.get("causal", True),
-                      kw.get("dropout_p", 0.0)))
-        return real_bwd(*a, **kw)
-
-    monkeypatch.setattr(attention, "_launch_fwd", fwd)
-    monkeypatch.setattr(attention, "_launch_bwd", bwd)
-    return calls
-
-
 def test_gpt2_routes_dropout_to_kernels(monkeypatch):
     from adapcc_amd.models.gpt2 import GPT2, GPT2Config
 
@@ -278,12 +257,12 @@ def test_gpt2_routes_dropout_to_kernels(monkeypatch):
     model = GPT2(cfg).to("cuda").to(torch.bfloat16)
     data = torch.randint(0, cfg.vocab_size, (2, 129), device="cuda")
     x, t = data[:, :-1], data[:, 1:].contiguous()
-    calls = _record_launches(monkeypatch)
+    calls = record_launches(monkeypatch)
 
     model.train()
     _, loss = model(x, t)
     loss.backward()
-    assert calls == [("fwd", True, 0.1), ("bwd", True, 0.1)]
+    assert calls == [("fwd", True, 0.1, False), ("bwd", True, 0.1, False)]
     assert torch.isfinite(loss)
     assert all(torch.isfinite(p.grad).all() for p in model.parameters()
                if p.grad is not None)
@@ -292,7 +271,7 @@ def test_gpt2_routes_dropout_to_kernels(monkeypatch):
     model.eval()
     with torch.no_grad():
         model(x, t)
-    assert calls == [("fwd", True, 0.0)]
+    assert calls == [("fwd", True, 0.0, False)]
 
 
 def test_vit_routes_dropout_to_kernels(monkeypatch):
@@ -303,17 +282,17 @@ def test_vit_routes_dropout_to_kernels(monkeypatch):
     torch.manual_seed(51)
     model = ViT(cfg).to("cuda").to(torch.bfloat16)
     x = torch.randn(2, 3, 32, 32, device="cuda", dtype=torch.bfloat16)
-    calls = _record_launches(monkeypatch)
+    calls = record_launches(monkeypatch)
 
     model.train()
     model(x).float().sum().backward()
-    assert calls == [("fwd", False, 0.1), ("bwd", False, 0.1)]
+    assert calls == [("fwd", False, 0.1, False), ("bwd", False, 0.1, False)]
 
     del calls[:]
     model.eval()
     with torch.no_grad():
         model(x)
-    assert calls == [("fwd", False, 0.0)]
+    assert calls == [("fwd", False, 0.0, False)]
 
 
 def test_reference_helper_reduces_to_plain_attention():

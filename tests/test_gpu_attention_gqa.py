@@ -19,7 +19,7 @@ import math
 import pytest
 import torch
 
-from attn_util import ref_attention_f32
+from attn_util import record_launches, ref_attention_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -448,22 +448,13 @@ def test_gpt2_grouped_runs_kernels_and_matches_repeated_weights(monkeypatch):
     qkv = grouped.h[0].attn.c_attn(grouped.wte(x))
     assert attention.fa_qkv_supported(qkv, H, 0.0, n_kv_head=Hk)
 
-    calls = []
-    real_fwd, real_bwd = attention._launch_fwd, attention._launch_bwd
-
-    def fwd(*a, **kw):
-        calls.append(("fwd", a[0].shape[1], a[1].shape[1]))
-        return real_fwd(*a, **kw)
-
-    def bwd(*a, **kw):
-        calls.append(("bwd", a[0].shape[1], a[1].shape[1]))
-        return real_bwd(*a, **kw)
-
-    monkeypatch.setattr(attention, "_launch_fwd", fwd)
-    monkeypatch.setattr(attention, "_launch_bwd", bwd)
+    # each entry ends in the head counts of q and k
+    calls = record_launches(
+        monkeypatch, extra=lambda q, k, *a: (q.shape[1], k.shape[1]))
     logits, loss = grouped(x, t)
     loss.backward()
-    assert calls == [("fwd", H, Hk)] * 2 + [("bwd", H, Hk)] * 2
+    assert calls == ([("fwd", True, 0.0, False, H, Hk)] * 2
+                     + [("bwd", True, 0.0, False, H, Hk)] * 2)
     assert torch.isfinite(loss)
     assert all(torch.isfinite(p.grad).all() for p in grouped.parameters())
     with torch.no_grad():

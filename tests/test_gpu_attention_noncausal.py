@@ -10,7 +10,7 @@ import pytest
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from attn_util import ref_attention_f32
+from attn_util import record_launches, ref_attention_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -228,7 +228,6 @@ def test_vit_block_takes_fast_path(monkeypatch):
     import torch.nn.functional as F
 
     from adapcc_amd.models.vit import EncoderBlock
-    from adapcc_amd.ops import attention
 
     torch.manual_seed(40)
     dim, heads, T = 768, 12, 197
@@ -249,24 +248,12 @@ def test_vit_block_takes_fast_path(monkeypatch):
         x = x + blk.proj(a)
         return x + blk.mlp(blk.ln2(x))
 
-    calls = []
-    real_fwd, real_bwd = attention._launch_fwd, attention._launch_bwd
-
-    def fwd(*a, **kw):
-        calls.append(("fwd", kw.get("causal", True)))
-        return real_fwd(*a, **kw)
-
-    def bwd(*a, **kw):
-        calls.append(("bwd", kw.get("causal", True)))
-        return real_bwd(*a, **kw)
-
-    monkeypatch.setattr(attention, "_launch_fwd", fwd)
-    monkeypatch.setattr(attention, "_launch_bwd", bwd)
+    calls = record_launches(monkeypatch)
 
     x_new = x.clone().requires_grad_(True)
     y_new = blk(x_new)
     y_new.backward(g)
-    assert calls == [("fwd", False), ("bwd", False)]
+    assert calls == [("fwd", False, 0.0, False), ("bwd", False, 0.0, False)]
 
     x_old = x.clone().requires_grad_(True)
     y_old = old_forward(x_old)

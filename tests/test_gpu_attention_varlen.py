@@ -10,7 +10,7 @@ import pytest
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from attn_util import ref_attention_f32
+from attn_util import record_launches, ref_attention_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -54,8 +54,8 @@ def seq4(t, a, b):
 
 def run_varlen(q, k, v, g, lens, causal, **kw):
     """o, lse, dq, dk, dv of one packed forward + backward."""
-    from adapcc_amd.ops.attention import (_fa_varlen_forward_lse,
-                                          fa_varlen_supported,
+    from adapcc_amd.ops.attention import (_fa_forward_lse, _rows4,
+                                          _varlen_plan, fa_varlen_supported,
                                           flash_attention_varlen)
 
     cu = cu_of(lens)
@@ -64,9 +64,11 @@ def run_varlen(q, k, v, g, lens, causal, **kw):
     o = flash_attention_varlen(qr, kr, vr, cu, causal=causal, **kw)
     o.backward(g)
     seed = kw.get("dropout_seed")
-    o2, lse, _ = _fa_varlen_forward_lse(
-        q, k, v, cu, SCALE, causal, dropout_p=kw.get("dropout_p", 0.0),
-        seed=seed)
+    o2, lse = _fa_forward_lse(
+        _rows4(q), _rows4(k), _rows4(v), SCALE, causal,
+        dropout_p=kw.get("dropout_p", 0.0), seed=seed,
+        tmap=_varlen_plan(cu, q.shape[0]))
+    o2, lse = o2[0].transpose(0, 1), lse[0]
     # (a poisoned sequence holds NaN in both, on purpose)
     torch.testing.assert_close(o.detach(), o2, rtol=0, atol=0,
                                equal_nan=True)
@@ -161,11 +163,12 @@ def test_matches_fp32_reference(data, packed, causal):
 
 @pytest.mark.parametrize("causal", [True, False])
 def test_lse_counts_keys(data, causal):
-    from adapcc_amd.ops.attention import _fa_varlen_forward_lse
+    from adapcc_amd.ops.attention import _fa_forward_lse, _varlen_plan
 
     q = torch.zeros_like(data["q"])
-    _, lse, _ = _fa_varlen_forward_lse(q, data["k"], data["v"], cu_of(LENS),
-                                       SCALE, causal)
+    _, lse = _fa_forward_lse(q, data["k"], data["v"], SCALE, causal,
+                             tmap=_varlen_plan(cu_of(LENS), TOTAL))
+    lse = lse[0]
     want = torch.empty(TOTAL, device="cuda")
     for _, a, b in spans(LENS):
         n = b - a
@@ -222,24 +225,22 @@ def _guarded_rows(fill):
 def _run_raw(causal, in_fill):
     """Forward + backward through the launch helpers on guarded buffers.
     Returns the result views and the (buffer, view) pairs of the outputs."""
-    from adapcc_amd.ops.attention import (_launch_varlen_bwd,
-                                          _launch_varlen_fwd, _rows4,
+    from adapcc_amd.ops.attention import (_launch_bwd, _launch_fwd, _rows4,
                                           _varlen_plan)
 
     sent = 1234.0  # exact in bf16 and fp32
     cu = cu_of(LENS)
-    n_seqs = len(LENS)
     q, k, v, do = (_guarded(10 + i, in_fill)[1] for i in range(4))
     outs = [_guarded(None, sent) for _ in range(4)]  # o, dq, dk, dv
     rows = [_guarded_rows(sent) for _ in range(2)]   # lse, delta
     o, dq, dk, dv = (view for _, view in outs)
     lse, delta = (view for _, view in rows)
     tmap = _varlen_plan(cu, TOTAL)
-    _launch_varlen_fwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o), lse, tmap,
-                       n_seqs, SCALE, causal=causal)
-    _launch_varlen_bwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o),
-                       _rows4(do), lse, _rows4(dq), _rows4(dk), _rows4(dv),
-                       tmap, n_seqs, SCALE, causal=causal, delta=delta)
+    _launch_fwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o), lse, SCALE,
+                causal=causal, tmap=tmap)
+    _launch_bwd(_rows4(q), _rows4(k), _rows4(v), _rows4(o), _rows4(do), lse,
+                _rows4(dq), _rows4(dk), _rows4(dv), SCALE, causal=causal,
+                delta=delta, tmap=tmap)
     torch.cuda.synchronize()
     return [o, lse, delta, dq, dk, dv], outs + rows
 
@@ -443,28 +444,6 @@ def _gpt2_cfg(**kw):
                       n_layer=2, n_head=2, **kw)
 
 
-def _record_varlen_launches(monkeypatch):
-    from adapcc_amd.ops import attention
-
-    calls = []
-    real_fwd = attention._launch_varlen_fwd
-    real_bwd = attention._launch_varlen_bwd
-
-    def fwd(*a, **kw):
-        calls.append(("fwd", kw.get("causal", True),
-                      kw.get("dropout_p", 0.0)))
-        return real_fwd(*a, **kw)
-
-    def bwd(*a, **kw):
-        calls.append(("bwd", kw.get("causal", True),
-                      kw.get("dropout_p", 0.0)))
-        return real_bwd(*a, **kw)
-
-    monkeypatch.setattr(attention, "_launch_varlen_fwd", fwd)
-    monkeypatch.setattr(attention, "_launch_varlen_bwd", bwd)
-    return calls
-
-
 def test_gpt2_packed_equals_per_document(monkeypatch):
     from adapcc_amd.models.gpt2 import GPT2
 
@@ -473,12 +452,13 @@ def test_gpt2_packed_equals_per_document(monkeypatch):
     model = GPT2(cfg).to("cuda").to(torch.bfloat16).eval()
     docs = [torch.randint(0, cfg.vocab_size, (n,), device="cuda")
             for n in DOCS]
-    calls = _record_varlen_launches(monkeypatch)
+    calls = record_launches(monkeypatch)
     with torch.no_grad():
         packed, _ = model(torch.cat(docs)[None], cu_seqlens=cu_of(DOCS))
-        assert calls == [("fwd", True, 0.0)] * cfg.n_layer
+        assert calls == [("fwd", True, 0.0, True)] * cfg.n_layer
         single = torch.cat([model(d[None])[0][0] for d in docs])
-    assert len(calls) == cfg.n_layer  # the single runs took other paths
+    # the single runs took other paths: no launch in either mode
+    assert calls == [("fwd", True, 0.0, True)] * cfg.n_layer
     torch.testing.assert_close(packed[0].float(), single.float(), rtol=2e-2,
                                atol=2e-2)
 
@@ -496,12 +476,12 @@ def test_gpt2_packed_training_step(monkeypatch):
         t = torch.roll(d, -1)
         t[-1] = -100  # no target across a document boundary
         targets.append(t)
-    calls = _record_varlen_launches(monkeypatch)
+    calls = record_launches(monkeypatch)
     _, loss = model(torch.cat(docs)[None], torch.cat(targets)[None],
                     cu_seqlens=cu_of(DOCS))
     loss.backward()
-    assert calls == ([("fwd", True, 0.1)] * cfg.n_layer
-                     + [("bwd", True, 0.1)] * cfg.n_layer)
+    assert calls == ([("fwd", True, 0.1, True)] * cfg.n_layer
+                     + [("bwd", True, 0.1, True)] * cfg.n_layer)
     assert torch.isfinite(loss)
     grads = [p.grad for p in model.parameters() if p.grad is not None]
     assert grads and all(torch.isfinite(x).all() for x in grads)
