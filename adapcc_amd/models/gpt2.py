@@ -5,7 +5,8 @@ small, trained on synthetic tokens — no network access for datasets).
 
 Attention runs through torch SDPA (rocm flash/mem-efficient backends);
 everything else is plain PyTorch so autograd works with DDP buckets the
-adapcc hook consumes.
+adapcc hook consumes. ``GPT2.generate`` samples greedily with a KV cache on
+the decode attention kernels.
 """
 
 from __future__ import annotations
@@ -64,10 +65,39 @@ class CausalSelfAttention(nn.Module):
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
         self.dropout = cfg.dropout
 
-    def forward(self, x: torch.Tensor,
-                cu_seqlens: torch.Tensor = None) -> torch.Tensor:
+    def _forward_cached(self, x: torch.Tensor, cache: dict) -> torch.Tensor:
+        """Generation (no dropout). cache: this layer's dict, ``Smax`` set.
+        Without ``lens`` the call is the prefill: ordinary attention over
+        the prompt x [B,T,C], whose k and v columns of the projection are
+        copied into new ``k``, ``v`` caches [B,Smax,Hk,D]. With ``lens``
+        (int32 [B] on the device) x is one token [B,1,C]: its k and v are
+        appended at row lens[b] and it attends over lens[b] + 1 keys."""
         from ..ops import attention
 
+        H, Hk = self.n_head, self.n_kv_head
+        qkv = self.c_attn(x)
+        B, T, W = qkv.shape
+        D = W // (H + 2 * Hk)
+        q, k, v = qkv.split([H * D, Hk * D, Hk * D], dim=-1)
+        if cache.get("lens") is None:
+            for name, t in (("k", k), ("v", v)):
+                cache[name] = qkv.new_zeros(B, cache["Smax"], Hk, D)
+                cache[name][:, :T] = t.view(B, T, Hk, D)
+            return self.c_proj(attention.flash_attention_qkv(
+                qkv, H, n_kv_head=Hk))
+        y = attention.flash_attention_decode(
+            q.view(B, H, D), cache["k"].transpose(1, 2),
+            cache["v"].transpose(1, 2), cache["lens"],
+            k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D))
+        return self.c_proj(y.view(B, 1, H * D))
+
+    def forward(self, x: torch.Tensor,
+                cu_seqlens: torch.Tensor = None,
+                cache: dict = None) -> torch.Tensor:
+        from ..ops import attention
+
+        if cache is not None:
+            return self._forward_cached(x, cache)
         p = self.dropout if self.training else 0.0
         if cu_seqlens is not None:
             # x is [1,total,C], documents back to back: attention stays
@@ -112,8 +142,11 @@ class Block(nn.Module):
         self.mlp = MLP(cfg)
 
     def forward(self, x: torch.Tensor,
-                cu_seqlens: torch.Tensor = None) -> torch.Tensor:
-        if cu_seqlens is None:
+                cu_seqlens: torch.Tensor = None,
+                cache: dict = None) -> torch.Tensor:
+        if cache is not None:
+            x = x + self.attn(self.ln_1(x), cache=cache)
+        elif cu_seqlens is None:
             x = x + self.attn(self.ln_1(x))
         else:
             x = x + self.attn(self.ln_1(x), cu_seqlens)
@@ -228,3 +261,47 @@ class GPT2(nn.Module):
                 logits.view(-1, logits.size(-1)), targets.view(-1)
             )
         return logits, loss
+
+    @torch.no_grad()
+    def generate(self, idx: torch.Tensor, max_new_tokens: int,
+                 return_logits: bool = False):
+        """Greedy continuation of equal-length prompts idx [B,T], T +
+        max_new_tokens <= n_positions: returns [B, T + max_new_tokens], and
+        with ``return_logits`` also the [B, max_new_tokens, vocab] logits
+        each new token was the argmax of.
+
+        The prompt runs through the ordinary forward once, each attention
+        layer keeping its k and v in a cache [B, T + max_new_tokens, Hk, D];
+        every further token is one pass over [B,1,C] whose attention is
+        ``flash_attention_decode`` with the token's k and v appended in
+        place. Lengths and position ids stay on the device: the loop has no
+        host sync. No dropout, whatever the module's mode."""
+        B, T = idx.shape
+        total = T + max_new_tokens
+        if T < 1 or max_new_tokens < 1 or total > self.cfg.n_positions:
+            raise ValueError("GPT2.generate: need a prompt, max_new_tokens "
+                             f">= 1 and T + max_new_tokens <= n_positions, "
+                             f"got T {T}, max_new_tokens {max_new_tokens}, "
+                             f"n_positions {self.cfg.n_positions}")
+        caches = [{"Smax": total} for _ in self.h]
+
+        def last_logits(x):
+            for block, cache in zip(self.h, caches):
+                x = block(x, cache=cache)
+            return self.lm_head(self.ln_f(x[:, -1:]))[:, 0]
+
+        pos = torch.arange(T, device=idx.device)
+        logits = [last_logits(self.wte(idx) + self.wpe(pos))]
+        tokens = [idx, logits[0].argmax(-1, keepdim=True)]
+        lens = torch.full((B,), T, dtype=torch.int32, device=idx.device)
+        for cache in caches:
+            cache["lens"] = lens
+        for _ in range(max_new_tokens - 1):
+            x = self.wte(tokens[-1]) + self.wpe(lens.long()).unsqueeze(1)
+            logits.append(last_logits(x))
+            tokens.append(logits[-1].argmax(-1, keepdim=True))
+            lens += 1      # every layer has appended this token's k and v
+        out = torch.cat(tokens, dim=1)
+        if return_logits:
+            return out, torch.stack(logits, dim=1)
+        return out

@@ -42,6 +42,19 @@ kernel path the same function is composed from torch SDPA under a
 block-diagonal mask. To everything between the entry points and the kernels
 this mode is the fixed-length call with B = 1, S = total and the map
 (``tmap``) as one more argument.
+
+``flash_attention_decode`` is the generation step: one new query row per
+sequence, q [B,H,D], against a KV cache [B,Hk,Smax,D] of which
+``cache_seqlens`` (int32 [B] on the device) says how many keys count, with
+the same head grouping. Its kernels (csrc/attn_decode.hip) split the keys,
+not the query rows, over workgroups, read every K/V byte once per K/V head
+for all H // Hk query heads, and merge the splits deterministically. The
+split count depends on the shapes alone, so there is no host sync either and
+a captured graph whose lengths are refilled stays valid. With ``k_new`` and
+``v_new`` the new token's rows are first written into the cache in place.
+Forward only. Off the kernel path it is composed from ``index_put`` and
+torch SDPA under a key-length mask. Longer queries against a longer key axis
+(cross-attention, chunked prefill) are not served by the kernels.
 """
 
 from __future__ import annotations
@@ -57,7 +70,8 @@ __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
            "fa_qkv_supported", "fa_dropout_mask",
            "dropout_keep_mask_reference", "flash_attention_varlen",
            "flash_attention_qkv_varlen", "fa_varlen_supported",
-           "fa_qkv_varlen_supported", "varlen_tile_map_reference"]
+           "fa_qkv_varlen_supported", "varlen_tile_map_reference",
+           "flash_attention_decode", "fa_decode_supported"]
 
 
 _QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
@@ -662,3 +676,211 @@ def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
                                dropout_p=dropout_p,
                                dropout_seed=dropout_seed)
     return y.contiguous().view(total, n_head * D)
+
+
+# ---------------------------------------------------------------------------
+# Decode: one query row per sequence against a KV cache
+# ---------------------------------------------------------------------------
+_DECODE_MAX_GROUP = 32  # csrc/attn_decode_plan.h's kDecodeMaxGroup
+
+
+def _rows_ok(t: torch.Tensor) -> bool:
+    """Rows (the last dimension) contiguous and 16-B aligned, whatever the
+    number of leading dimensions: ``_row_ok`` for q and k_new too."""
+    if t.stride(-1) != 1 or t.data_ptr() % 16 != 0:
+        return False
+    return all(s % 8 == 0 for s in t.stride()[:-1])
+
+
+def _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new) -> None:
+    name = "flash_attention_decode"
+    if q.dim() != 3 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError(f"{name}: need q [B,H,D] and k_cache, v_cache "
+                         f"[B,Hk,Smax,D] of one shape, got {tuple(q.shape)}, "
+                         f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
+    B, H, D = q.shape
+    Bk, Hk, Smax, Dk = k_cache.shape
+    if Bk != B or Dk != D or min(B, H, Hk, Smax, D) < 1:
+        raise ValueError(f"{name}: q {tuple(q.shape)} and the caches "
+                         f"{tuple(k_cache.shape)} do not agree in batch and "
+                         "head_dim (or a dimension is empty)")
+    if H % Hk != 0:
+        raise ValueError(f"{name}: the K/V head count must divide q's, got "
+                         f"{H} and {Hk}")
+    if not (q.dtype == k_cache.dtype == v_cache.dtype):
+        raise ValueError(f"{name}: q and the caches must have one dtype, got "
+                         f"{q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+    if not (q.device == k_cache.device == v_cache.device):
+        raise ValueError(f"{name}: q and the caches must be on one device")
+    if not isinstance(cache_seqlens, torch.Tensor):
+        raise ValueError(f"{name}: cache_seqlens must be a tensor")
+    if cache_seqlens.dtype != torch.int32:
+        raise ValueError(f"{name}: cache_seqlens must be int32, got "
+                         f"{cache_seqlens.dtype}")
+    if cache_seqlens.shape != (B,):
+        raise ValueError(f"{name}: cache_seqlens must be [B] = [{B}], got "
+                         f"{tuple(cache_seqlens.shape)}")
+    if cache_seqlens.device != q.device:
+        raise ValueError(f"{name}: cache_seqlens is on "
+                         f"{cache_seqlens.device}, the inputs on {q.device}")
+    if (k_new is None) != (v_new is None):
+        raise ValueError(f"{name}: pass k_new and v_new together or neither")
+    for n, t in (("k_new", k_new), ("v_new", v_new)):
+        if t is None:
+            continue
+        if (t.shape != (B, Hk, D) or t.dtype != q.dtype
+                or t.device != q.device):
+            raise ValueError(f"{name}: {n} must be [B,Hk,D] = "
+                             f"[{B},{Hk},{D}] of q's dtype and device, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
+                        v_cache: torch.Tensor,
+                        cache_seqlens: torch.Tensor) -> bool:
+    """True where ``flash_attention_decode`` runs its kernels: bf16 on the
+    GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
+    contiguous and 16-B aligned, extension built."""
+    try:
+        _check_decode(q, k_cache, v_cache, cache_seqlens, None, None)
+    except ValueError:
+        return False
+    return _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens)
+
+
+def _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens) -> bool:
+    """``fa_decode_supported`` for arguments ``_check_decode`` has passed."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16):
+        return False
+    if q.shape[2] not in (64, 128):
+        return False
+    if q.shape[1] // k_cache.shape[1] > _DECODE_MAX_GROUP:
+        return False
+    if not (_rows_ok(q) and _row_ok(k_cache) and _row_ok(v_cache)):
+        return False
+    if not cache_seqlens.is_contiguous():
+        return False
+    return bool(_core())
+
+
+def _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
+                   num_splits, return_lse):
+    """The kernel path, for arguments that passed ``_check_decode`` and
+    ``_decode_kernel_ok``."""
+    core = _core()
+    B, H, D = q.shape
+    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
+    dev = q.get_device()  # the launcher makes it current for the call
+    ns = core.fa_decode_splits(B, Hk, Smax,
+                               0 if num_splits is None else int(num_splits),
+                               dev)
+    out = torch.empty((B, H, D), dtype=q.dtype, device=q.device)
+    lse = (torch.empty((B, H), dtype=torch.float32, device=q.device)
+           if return_lse else None)
+    kw = {}
+    if ns > 1:
+        o_part = torch.empty((B, H, ns, D), dtype=torch.float32,
+                             device=q.device)
+        lse_part = torch.empty((B, H, ns), dtype=torch.float32,
+                               device=q.device)
+        kw.update(o_part=o_part.data_ptr(), lse_part=lse_part.data_ptr())
+    new_strides = [0, 0, 0, 0]
+    if k_new is not None:
+        k_new = k_new if _rows_ok(k_new) else k_new.contiguous()
+        v_new = v_new if _rows_ok(v_new) else v_new.contiguous()
+        kw.update(k_new=k_new.data_ptr(), v_new=v_new.data_ptr())
+        new_strides = [k_new.stride(0), k_new.stride(1), v_new.stride(0),
+                       v_new.stride(1)]
+    strides = ([q.stride(0), q.stride(1)] + _strides3(k_cache)
+               + _strides3(v_cache) + new_strides)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    core.fa_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                   cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Smax,
+                   D, strides, scale, ns, dev, stream,
+                   lse=lse.data_ptr() if return_lse else 0, **kw)
+    return (out, lse) if return_lse else out
+
+
+def _decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
+                     return_lse):
+    """index_put for the append, then SDPA under the [B,1,1,Smax] key-length
+    mask; no host sync. A sequence with no key gives a zero row."""
+    B, H, D = q.shape
+    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
+    lens = cache_seqlens.clamp(0, Smax)
+    if k_new is not None:
+        # a full cache is left alone: index Smax - 1 gets its own old row
+        room = (lens < Smax).view(B, 1, 1)
+        at = lens.clamp(max=Smax - 1).long()
+        rows = torch.arange(B, device=q.device)
+        # indexed assignment is index_put_
+        k_cache[rows, :, at] = torch.where(room, k_new, k_cache[rows, :, at])
+        v_cache[rows, :, at] = torch.where(room, v_new, v_cache[rows, :, at])
+        lens = (lens + 1).clamp(max=Smax)
+    keys = torch.arange(Smax, device=q.device).view(1, 1, 1, Smax)
+    mask = keys < lens.view(B, 1, 1, 1)
+    some = (lens > 0).view(B, 1, 1)
+    # rows past a sequence's length may hold anything, NaN included
+    kz = torch.where(mask.view(B, 1, Smax, 1), k_cache, 0)
+    vz = torch.where(mask.view(B, 1, Smax, 1), v_cache, 0)
+    gqa = {"enable_gqa": True} if Hk != H else {}
+    # an all-masked row would be NaN: let it see key 0, zero it afterwards
+    y = torch.nn.functional.scaled_dot_product_attention(
+        q.unsqueeze(2), kz, vz, attn_mask=mask | ~some.view(B, 1, 1, 1),
+        scale=scale, **gqa).squeeze(2)
+    y = torch.where(some, y, 0)
+    if not return_lse:
+        return y
+    s = scale if scale is not None else 1.0 / math.sqrt(D)
+    G = H // Hk
+    sc = torch.einsum("bhgd,bhkd->bhgk", q.float().view(B, Hk, G, D),
+                      kz.float()) * s
+    sc = sc.masked_fill(~mask, float("-inf"))
+    return y, torch.logsumexp(sc, dim=-1).view(B, H)
+
+
+def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
+                           v_cache: torch.Tensor,
+                           cache_seqlens: torch.Tensor,
+                           k_new: Optional[torch.Tensor] = None,
+                           v_new: Optional[torch.Tensor] = None,
+                           scale: float = None,
+                           num_splits: Optional[int] = None,
+                           return_lse: bool = False):
+    """Attention of one new token per sequence over a KV cache. q: [B,H,D];
+    k_cache, v_cache: [B,Hk,Smax,D] with H % Hk == 0 and any batch, head and
+    row strides (a [B,Smax,Hk,D] cache goes in as its transposed view), query
+    head h reading K/V head h // (H // Hk); cache_seqlens: int32 [B] on the
+    same device, the number of keys of each sequence that count. Returns
+    [B,H,D], with ``return_lse`` also the fp32 [B,H] natural-log logsumexp
+    of the scaled scores. A sequence of length 0 gives a zero row and lse
+    -inf.
+
+    With k_new and v_new ([B,Hk,D], both or neither) the new token's rows
+    are first written into cache row cache_seqlens[b], in place, and the
+    attention covers cache_seqlens[b] + 1 keys. cache_seqlens itself is
+    never modified, and never read on the host: the caller advances it.
+    Lengths are clamped to [0, Smax]; appending to a full cache is the
+    caller's error and gives unspecified values, but no access outside the
+    tensors.
+
+    bf16 on the GPU with D = 64 or 128 and H // Hk <= 32 runs the CDNA4
+    split-KV kernels; num_splits None lets the shapes decide the number of
+    key splits, an integer asks for that many (the kernels only). Anything
+    else is composed from index_put and torch SDPA. Forward only."""
+    _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new)
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad
+            for t in (q, k_cache, v_cache, k_new, v_new)):
+        raise RuntimeError("flash_attention_decode: forward only, but an "
+                           "input requires grad; call it under "
+                           "torch.no_grad()")
+    if num_splits is not None and int(num_splits) < 1:
+        raise ValueError("flash_attention_decode: num_splits must be None or "
+                         f">= 1, got {num_splits}")
+    if _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens):
+        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        return _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new,
+                              v_new, s, num_splits, return_lse)
+    return _decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                            scale, return_lse)

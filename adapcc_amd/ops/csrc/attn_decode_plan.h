@@ -1,0 +1,78 @@
+// Host-only part of the decode attention (attn_decode.hip): the argument
+// checks and the split policy. No device code and no HIP header, so
+// tests/cpp/decode_plan_sanitize.cpp can build it with a host compiler under
+// ASan + UBSan.
+#pragma once
+
+#include <stdexcept>
+#include <string>
+
+namespace adapcc {
+
+// Keys one workgroup pass covers: 4 waves x one 32-key sub-tile each. A
+// split is a multiple of it, so every split starts on a wave-0 sub-tile.
+constexpr int kDecodeWgKeys = 128;
+// Target: this many workgroups per CU over the whole launch, at most
+// kDecodeMaxSplits splits of one (batch, K/V head), and no split shorter
+// than kDecodeMinSplitKeys of capacity. Settled on the MI355X with
+// benchmarks/attn_bench.py --shape decode --sweep
+// (profiles/attn_decode_sweep.txt); the figures are in attn_decode.hip's
+// header.
+constexpr int kDecodeWgPerCu = 2;
+constexpr int kDecodeMaxSplits = 16;
+constexpr int kDecodeMinSplitKeys = 1024;
+// Query heads per K/V head the kernel takes: the 32 columns of one MFMA tile.
+constexpr int kDecodeMaxGroup = 32;
+
+struct DecodePlan {
+  int n_splits;  // workgroups along the keys of one (batch, K/V head)
+  int L;         // keys per split, a multiple of kDecodeWgKeys
+};
+
+inline void decode_check_shapes(const char* name, long B, long H, long Hk,
+                                long Smax, long head_dim) {
+  const std::string n(name);
+  if (B < 1 || H < 1 || Hk < 1 || Smax < 1)
+    throw std::runtime_error(n + ": empty shape");
+  if (head_dim != 64 && head_dim != 128)
+    throw std::runtime_error(n + ": head_dim must be 64 or 128, got " +
+                             std::to_string(head_dim));
+  if (H % Hk != 0)
+    throw std::runtime_error(n + ": n_kv_head must divide H, got H " +
+                             std::to_string(H) + ", n_kv_head " +
+                             std::to_string(Hk));
+  if (H / Hk > kDecodeMaxGroup)
+    throw std::runtime_error(n + ": at most 32 query heads per K/V head, "
+                             "got " + std::to_string(H / Hk));
+  // grid (n_splits, Hk, B), and int key indices up to Smax + L
+  if (B > 65535 || Hk > 65535 || Smax > (1L << 30))
+    throw std::runtime_error(n + ": shape too large");
+}
+
+// Splits of a cache of capacity Smax. `requested` <= 0 is the policy:
+// enough splits that B * Hk * n_splits workgroups fill the chip
+// kDecodeWgPerCu times over, within the two limits above. `requested` >= 1 asks
+// for that many. Either way a split is a multiple of 128 keys, so the count
+// that comes back can be smaller than the one asked for. Shapes only: the
+// lengths never enter, so nothing has to be read back from the device and a
+// captured graph stays valid when the lengths change.
+inline DecodePlan decode_split_plan(long B, long Hk, long Smax, int n_cu,
+                                    int requested) {
+  const long max_splits = (Smax + kDecodeWgKeys - 1) / kDecodeWgKeys;
+  long n = requested;
+  if (n <= 0) {
+    const long groups = B * Hk;
+    const long want = (long)kDecodeWgPerCu * (n_cu > 0 ? n_cu : 1);
+    n = (want + groups - 1) / groups;
+    if (n > kDecodeMaxSplits) n = kDecodeMaxSplits;
+    if (n > Smax / kDecodeMinSplitKeys) n = Smax / kDecodeMinSplitKeys;
+  }
+  if (n > max_splits) n = max_splits;
+  if (n < 1) n = 1;
+  long L = (Smax + n - 1) / n;
+  L = (L + kDecodeWgKeys - 1) / kDecodeWgKeys * kDecodeWgKeys;
+  n = (Smax + L - 1) / L;
+  return {(int)n, (int)L};
+}
+
+}  // namespace adapcc

@@ -122,6 +122,12 @@ void fa_dropout_mask(uint8_t* out, const long* seed, int B, int H, int S,
                      double dropout_p, hipStream_t stream);
 void fa_varlen_plan(const int* cu_seqlens, int n_seqs, int total, int* tmap,
                     hipStream_t stream);
+int fa_decode_splits(int B, int Hk, int Smax, int num_splits, int device);
+void fa_decode(const void* q, void* k_cache, void* v_cache,
+               const int* seqlens, const void* k_new, const void* v_new,
+               void* out, float* lse, float* o_part, float* lse_part, int B,
+               int H, int Hk, int Smax, int head_dim, const long* strides,
+               float scale, int n_splits, int device, hipStream_t stream);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -396,6 +402,43 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("cu_seqlens"), py::arg("n_seqs"), py::arg("total"),
         py::arg("tmap"), py::arg("stream"));
+  // Decode attention over a KV cache (attn_decode.hip). q [B,H,head_dim],
+  // caches [B,Hk,Smax,head_dim], seqlens int32 [B] on the device, out bf16
+  // [B,H,head_dim] contiguous, lse fp32 [B,H] or 0. strides: q (b, h),
+  // k_cache and v_cache (b, h, row), k_new and v_new (b, h). n_splits is
+  // what fa_decode_splits gives for the shapes (num_splits <= 0: policy);
+  // above 1, o_part fp32 [B,H,n_splits,head_dim] and lse_part fp32
+  // [B,H,n_splits] are the workspaces. k_new, v_new != 0: the rows are
+  // appended at seqlens[b] first. device: the tensors' device index, made
+  // current for the call (stream is one of its streams). Nothing reads
+  // seqlens on the host.
+  m.def("fa_decode_splits", &adapcc::fa_decode_splits, py::arg("B"),
+        py::arg("Hk"), py::arg("Smax"), py::arg("num_splits"),
+        py::arg("device"));
+  m.def("fa_decode",
+        [](uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+           uintptr_t seqlens, uintptr_t out, int B, int H, int Hk, int Smax,
+           int head_dim, const std::vector<long>& strides, float scale,
+           int n_splits, int device, uintptr_t stream, uintptr_t k_new,
+           uintptr_t v_new, uintptr_t lse, uintptr_t o_part,
+           uintptr_t lse_part) {
+          if (strides.size() != 12)
+            throw std::runtime_error("fa_decode: need 12 strides");
+          adapcc::fa_decode((const void*)q, (void*)k_cache, (void*)v_cache,
+                            (const int*)seqlens, (const void*)k_new,
+                            (const void*)v_new, (void*)out, (float*)lse,
+                            (float*)o_part, (float*)lse_part, B, H, Hk, Smax,
+                            head_dim, strides.data(), scale, n_splits, device,
+                            reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seqlens"), py::arg("out"), py::arg("B"), py::arg("H"),
+        py::arg("Hk"), py::arg("Smax"), py::arg("head_dim"),
+        py::arg("strides"), py::arg("scale"), py::arg("n_splits"),
+        py::arg("device"), py::arg("stream"), py::arg("k_new") = 0, py::arg("v_new") = 0,
+        py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

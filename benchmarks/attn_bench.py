@@ -1,7 +1,7 @@
 """Flash-attention kernel timing: hand-written CDNA4 kernels vs torch SDPA.
 
 Run on a GPU box:  python benchmarks/attn_bench.py
-                       [--shape gpt2|vit|gpt2-d128|vit-d128|varlen]
+                       [--shape gpt2|vit|gpt2-d128|vit-d128|varlen|decode]
                        [--dropout P] [--head-dim 64|128] [--kv-heads N]
 
 gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
@@ -21,6 +21,17 @@ GQA costs without it: K/V repeat_interleave'd to H heads in front of the
 same kernels and autograd summing dk/dv over the group, with those passes
 and (K/V expanded beforehand, per-head dk/dv left as they are) without, and
 (c) torch SDPA with enable_gqa=True.
+decode: one query row per sequence over a full KV cache of 1024 and 16384
+keys, B 1 and 32; --head-dim 128 is H16 with 16, 4 and 1 K/V heads,
+--head-dim 64 H12 with 12 and 1 (--kv-heads N: that count alone). Times,
+alternating in one process, flash_attention_decode (and, as "no checks",
+the launch helper under it: the difference is what the entry point's
+argument checks cost on the host) against torch SDPA under the key-length mask
+with enable_gqa and against this project's flash_attention(causal=False) on
+the one-row query (which, its kernels being self-attention only, resolves to
+SDPA without a mask on the cache cut to the common length), and prints microseconds and the K/V bytes per second,
+2 * B * Hk * len * D * 2 bytes over the time. --sweep adds forced split
+counts, the measurement behind the split policy's constants.
 """
 import argparse
 import math
@@ -56,8 +67,10 @@ def main():
     from adapcc_amd.ops.attention import fa_supported, flash_attention
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", choices=sorted(SHAPES) + ["varlen"],
+    ap.add_argument("--shape", choices=sorted(SHAPES) + ["varlen", "decode"],
                     default="gpt2")
+    ap.add_argument("--sweep", action="store_true",
+                    help="decode only: also time forced split counts")
     ap.add_argument("--iters", type=int, default=None,
                     help="timed calls per figure (default 20; 200 for vit, "
                          "whose calls are ~10x shorter)")
@@ -70,6 +83,8 @@ def main():
                          "grouped-query comparison instead of the usual one")
     args = ap.parse_args()
     drop = args.dropout
+    if args.shape == "decode":
+        return decode_path(args.head_dim, args.kv_heads, args.sweep)
     if args.shape == "varlen":
         H = 12 * 64 // args.head_dim
         if args.kv_heads:
@@ -158,6 +173,65 @@ def alternate(fns, window=0.5, rounds=5):
             per_round[name].append(bench(fn, iters=calls[name], warmup=0))
     return {name: (sum(r) / len(r), min(r), max(r))
             for name, r in per_round.items()}
+
+
+def decode_path(D, kv_heads, sweep):
+    from adapcc_amd.ops.attention import (_launch_decode, fa_decode_supported,
+                                          fa_supported, flash_attention,
+                                          flash_attention_decode)
+
+    H = 16 if D == 128 else 12
+    kv = [kv_heads] if kv_heads else ([16, 4, 1] if D == 128 else [12, 1])
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    scale = 1.0 / math.sqrt(D)
+    for B in (1, 32):
+        for Hk in kv:
+            for n in (1024, 16384):
+                torch.manual_seed(0)
+                q = torch.randn(B, H, D, device="cuda", dtype=torch.bfloat16)
+                k = torch.randn(B, Hk, n, D, device="cuda",
+                                dtype=torch.bfloat16)
+                v = torch.randn_like(k)
+                lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                mask = (torch.arange(n, device="cuda").view(1, 1, 1, n)
+                        < lens.view(B, 1, 1, 1))
+                q4 = q.unsqueeze(2)
+                # a missing kernel is an error, not a silent SDPA-vs-SDPA run
+                assert fa_decode_supported(q, k, v, lens)
+                # the training kernels take q, k, v of one length only, so
+                # flash_attention hands this shape to SDPA (no mask: the
+                # cache is cut to the common length, here all of it)
+                assert not fa_supported(q4, k, v, False, 0.0)
+                fns = {
+                    "decode": lambda: flash_attention_decode(q, k, v, lens),
+                    "decode, no checks": lambda: _launch_decode(
+                        q, k, v, lens, None, None, scale, None, False),
+                    "sdpa masked": lambda: sdpa(q4, k, v, attn_mask=mask,
+                                                enable_gqa=Hk != H),
+                    "flash_attention->sdpa": lambda: flash_attention(
+                        q4, k, v, causal=False),
+                }
+                if sweep:
+                    for ns in (1, 4, 16, 32, 64, 128):
+                        fns[f"decode splits={ns}"] = (
+                            lambda ns=ns: flash_attention_decode(
+                                q, k, v, lens, num_splits=ns))
+                ref = sdpa(q4.float(), k.float(), v.float(),
+                           enable_gqa=Hk != H).squeeze(2)
+                err = (flash_attention_decode(q, k, v, lens).float()
+                       - ref).abs().max().item()
+                nbytes = 2 * B * Hk * n * D * 2
+                print(f"B{B} H{H} Hk{Hk} D{D} len{n}  "
+                      f"(K/V {nbytes / 2**20:.1f} MiB, max err vs fp32 "
+                      f"{err:.2e})")
+                base = None
+                for name, (ms, lo, hi) in alternate(fns, window=0.3).items():
+                    base = base or ms
+                    print(f"  {name:<22} {ms * 1e3:9.1f} us  (rounds "
+                          f"{lo * 1e3:.1f}..{hi * 1e3:.1f})  "
+                          f"{nbytes / ms / 1e9:6.2f} TB/s  "
+                          f"this/decode {ms / base:.2f}")
+                del q, k, v, mask, ref
 
 
 def report(title, res, flops):
