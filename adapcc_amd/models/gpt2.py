@@ -66,12 +66,16 @@ class CausalSelfAttention(nn.Module):
         self.dropout = cfg.dropout
 
     def _forward_cached(self, x: torch.Tensor, cache: dict) -> torch.Tensor:
-        """Generation (no dropout). cache: this layer's dict, ``Smax`` set.
-        Without ``lens`` the call is the prefill: ordinary attention over
-        the prompt x [B,T,C], whose k and v columns of the projection are
-        copied into new ``k``, ``v`` caches [B,Smax,Hk,D]. With ``lens``
-        (int32 [B] on the device) x is one token [B,1,C]: its k and v are
-        appended at row lens[b] and it attends over lens[b] + 1 keys."""
+        """Generation (no dropout). cache: this layer's dict, ``Smax`` set;
+        ``k``, ``v`` [B,Smax,Hk,D] are made on the first call, uninitialised:
+        no row is read before it is written. ``lens`` (int32 [B] on the
+        device, absent: zeros) counts the keys each sequence holds. x
+        [B,T,C] is a block of T new positions, of which the first
+        ``q_lens[b]`` (int32 [B], absent: all) are real: one
+        ``flash_attention_extend`` call appends their k and v at row
+        lens[b] and attends row i over lens[b] + i + 1 keys, straight off
+        the projection. One token onto an existing cache with no ``q_lens``
+        is the decode step, ``flash_attention_decode``."""
         from ..ops import attention
 
         H, Hk = self.n_head, self.n_kv_head
@@ -79,17 +83,25 @@ class CausalSelfAttention(nn.Module):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hk)
         q, k, v = qkv.split([H * D, Hk * D, Hk * D], dim=-1)
-        if cache.get("lens") is None:
-            for name, t in (("k", k), ("v", v)):
-                cache[name] = qkv.new_zeros(B, cache["Smax"], Hk, D)
-                cache[name][:, :T] = t.view(B, T, Hk, D)
-            return self.c_proj(attention.flash_attention_qkv(
-                qkv, H, n_kv_head=Hk))
-        y = attention.flash_attention_decode(
-            q.view(B, H, D), cache["k"].transpose(1, 2),
-            cache["v"].transpose(1, 2), cache["lens"],
-            k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D))
-        return self.c_proj(y.view(B, 1, H * D))
+        if T == 1 and "k" in cache and cache.get("q_lens") is None:
+            y = attention.flash_attention_decode(
+                q.view(B, H, D), cache["k"].transpose(1, 2),
+                cache["v"].transpose(1, 2), cache["lens"],
+                k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D))
+            return self.c_proj(y.view(B, 1, H * D))
+        if "k" not in cache:
+            cache["k"] = qkv.new_empty(B, cache["Smax"], Hk, D)
+            cache["v"] = qkv.new_empty(B, cache["Smax"], Hk, D)
+        lens = cache.get("lens")
+        if lens is None:
+            lens = torch.zeros(B, dtype=torch.int32, device=x.device)
+        y = attention.flash_attention_extend(
+            q.view(B, T, H, D).transpose(1, 2), cache["k"].transpose(1, 2),
+            cache["v"].transpose(1, 2), lens,
+            k_new=k.view(B, T, Hk, D).transpose(1, 2),
+            v_new=v.view(B, T, Hk, D).transpose(1, 2),
+            q_lens=cache.get("q_lens"))
+        return self.c_proj(y.transpose(1, 2).view(B, T, H * D))
 
     def forward(self, x: torch.Tensor,
                 cu_seqlens: torch.Tensor = None,
@@ -264,18 +276,30 @@ class GPT2(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int,
-                 return_logits: bool = False):
-        """Greedy continuation of equal-length prompts idx [B,T], T +
-        max_new_tokens <= n_positions: returns [B, T + max_new_tokens], and
-        with ``return_logits`` also the [B, max_new_tokens, vocab] logits
-        each new token was the argmax of.
+                 return_logits: bool = False,
+                 prompt_lens: torch.Tensor = None,
+                 prefill_chunk: int = None):
+        """Greedy continuation of the prompts idx [B,T], T + max_new_tokens
+        <= n_positions: returns [B, T + max_new_tokens], and with
+        ``return_logits`` also the [B, max_new_tokens, vocab] logits each
+        new token was the argmax of.
 
-        The prompt runs through the ordinary forward once, each attention
-        layer keeping its k and v in a cache [B, T + max_new_tokens, Hk, D];
-        every further token is one pass over [B,1,C] whose attention is
-        ``flash_attention_decode`` with the token's k and v appended in
-        place. Lengths and position ids stay on the device: the loop has no
-        host sync. No dropout, whatever the module's mode."""
+        ``prompt_lens`` (int32 [B] on idx's device, each in 1..T) makes the
+        batch ragged: idx is right-padded with any valid token id, sequence
+        b's prompt is its first prompt_lens[b] tokens, its first new token
+        comes from the logits at position prompt_lens[b] - 1 and it
+        continues from there. The return value is then the
+        [B, max_new_tokens] new tokens alone (a ragged batch has no
+        rectangular concatenation). ``prefill_chunk`` sends the prompt
+        through the layers that many positions at a time.
+
+        Each attention layer keeps its k and v in a cache
+        [B, T + max_new_tokens, Hk, D]. The prompt's attention is
+        ``flash_attention_extend``, which appends a chunk's k and v rows and
+        attends in one pass at any length; every further token is one pass
+        over [B,1,C] through ``flash_attention_decode``. Lengths and
+        position ids stay on the device: neither the prefill nor the loop
+        has a host sync. No dropout, whatever the module's mode."""
         B, T = idx.shape
         total = T + max_new_tokens
         if T < 1 or max_new_tokens < 1 or total > self.cfg.n_positions:
@@ -283,25 +307,58 @@ class GPT2(nn.Module):
                              f">= 1 and T + max_new_tokens <= n_positions, "
                              f"got T {T}, max_new_tokens {max_new_tokens}, "
                              f"n_positions {self.cfg.n_positions}")
+        chunk = T if prefill_chunk is None else int(prefill_chunk)
+        if chunk < 1:
+            raise ValueError("GPT2.generate: prefill_chunk must be >= 1, got "
+                             f"{prefill_chunk}")
+        ragged = prompt_lens is not None
+        if ragged:
+            if (prompt_lens.dtype != torch.int32 or prompt_lens.shape != (B,)
+                    or prompt_lens.device != idx.device):
+                raise ValueError("GPT2.generate: prompt_lens must be int32 "
+                                 f"[{B}] on idx's device")
+            plens = prompt_lens.clamp(1, T)
+        else:
+            plens = torch.full((B,), T, dtype=torch.int32, device=idx.device)
         caches = [{"Smax": total} for _ in self.h]
 
-        def last_logits(x):
+        def hidden(x):
             for block, cache in zip(self.h, caches):
                 x = block(x, cache=cache)
-            return self.lm_head(self.ln_f(x[:, -1:]))[:, 0]
+            return x
 
-        pos = torch.arange(T, device=idx.device)
-        logits = [last_logits(self.wte(idx) + self.wpe(pos))]
-        tokens = [idx, logits[0].argmax(-1, keepdim=True)]
-        lens = torch.full((B,), T, dtype=torch.int32, device=idx.device)
+        def head(x):      # x [B,C]
+            return self.lm_head(self.ln_f(x.unsqueeze(1)))[:, 0]
+
+        # prefill: last[b] is the hidden state at position plens[b] - 1
+        batch = torch.arange(B, device=idx.device)
+        last = None
+        for c0 in range(0, T, chunk):
+            n = min(chunk, T - c0)
+            for cache in caches:
+                cache["lens"] = plens.clamp(max=c0)
+                cache["q_lens"] = (plens - c0).clamp(0, n) if ragged else None
+            pos = torch.arange(c0, c0 + n, device=idx.device)
+            x = hidden(self.wte(idx[:, c0:c0 + n]) + self.wpe(pos))
+            if not ragged:
+                last = x[:, -1]
+                continue
+            at = plens - 1 - c0
+            here = ((at >= 0) & (at < n)).view(B, 1)
+            xa = x[batch, at.clamp(0, n - 1).long()]
+            last = xa if last is None else torch.where(here, xa, last)
+        logits = [head(last)]
+        tokens = [logits[0].argmax(-1, keepdim=True)]
+        lens = plens.clone()
         for cache in caches:
             cache["lens"] = lens
+            cache["q_lens"] = None
         for _ in range(max_new_tokens - 1):
             x = self.wte(tokens[-1]) + self.wpe(lens.long()).unsqueeze(1)
-            logits.append(last_logits(x))
+            logits.append(head(hidden(x)[:, 0]))
             tokens.append(logits[-1].argmax(-1, keepdim=True))
             lens += 1      # every layer has appended this token's k and v
-        out = torch.cat(tokens, dim=1)
+        out = torch.cat(tokens if ragged else [idx] + tokens, dim=1)
         if return_logits:
             return out, torch.stack(logits, dim=1)
         return out

@@ -53,8 +53,19 @@ split count depends on the shapes alone, so there is no host sync either and
 a captured graph whose lengths are refilled stays valid. With ``k_new`` and
 ``v_new`` the new token's rows are first written into the cache in place.
 Forward only. Off the kernel path it is composed from ``index_put`` and
-torch SDPA under a key-length mask. Longer queries against a longer key axis
-(cross-attention, chunked prefill) are not served by the kernels.
+torch SDPA under a key-length mask.
+
+``flash_attention_extend`` is the same over a block of rows: q [B,H,Sq,D]
+against the cache, optionally appending the block's own k and v rows
+([B,Hk,Sq,D]) first, with ``q_lens`` for a ragged block. Causal, row i sees
+keys up to total_b - n_b + i (bottom-right aligned: chunked prefill, a
+further turn on a kept cache, drafted tokens); non-causal it is
+cross-attention over the cached keys. Its kernel (csrc/attn_extend.hip)
+gives a workgroup one K/V head and 128 rows of the flattened (position, query
+head) axis, so a K/V tile is staged once for all H // Hk heads and a short
+chunk under GQA still fills its MFMA columns. No host sync; forward only. A
+short chunk over a long cache is not split over the keys, so it leaves most
+of the chip idle.
 """
 
 from __future__ import annotations
@@ -71,7 +82,8 @@ __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
            "dropout_keep_mask_reference", "flash_attention_varlen",
            "flash_attention_qkv_varlen", "fa_varlen_supported",
            "fa_qkv_varlen_supported", "varlen_tile_map_reference",
-           "flash_attention_decode", "fa_decode_supported"]
+           "flash_attention_decode", "fa_decode_supported",
+           "flash_attention_extend", "fa_extend_supported"]
 
 
 _QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
@@ -692,15 +704,20 @@ def _rows_ok(t: torch.Tensor) -> bool:
     return all(s % 8 == 0 for s in t.stride()[:-1])
 
 
-def _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new) -> None:
-    name = "flash_attention_decode"
-    if q.dim() != 3 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
-        raise ValueError(f"{name}: need q [B,H,D] and k_cache, v_cache "
+def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                  q_lens=None) -> None:
+    """The argument checks of the calls over a KV cache. q is [B,H,D]
+    (decode) or [B,H,Sq,D] (extend), new rows then [B,Hk,D] or [B,Hk,Sq,D];
+    q_lens (extend) like cache_seqlens."""
+    rows = "" if name.endswith("decode") else "Sq,"
+    if (q.dim() != (4 if rows else 3) or k_cache.dim() != 4
+            or k_cache.shape != v_cache.shape):
+        raise ValueError(f"{name}: need q [B,H,{rows}D] and k_cache, v_cache "
                          f"[B,Hk,Smax,D] of one shape, got {tuple(q.shape)}, "
                          f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
-    B, H, D = q.shape
+    B, H, D = q.shape[0], q.shape[1], q.shape[-1]
     Bk, Hk, Smax, Dk = k_cache.shape
-    if Bk != B or Dk != D or min(B, H, Hk, Smax, D) < 1:
+    if Bk != B or Dk != D or min(*q.shape, Hk, Smax) < 1:
         raise ValueError(f"{name}: q {tuple(q.shape)} and the caches "
                          f"{tuple(k_cache.shape)} do not agree in batch and "
                          "head_dim (or a dimension is empty)")
@@ -712,27 +729,41 @@ def _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new) -> None:
                          f"{q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
     if not (q.device == k_cache.device == v_cache.device):
         raise ValueError(f"{name}: q and the caches must be on one device")
-    if not isinstance(cache_seqlens, torch.Tensor):
-        raise ValueError(f"{name}: cache_seqlens must be a tensor")
-    if cache_seqlens.dtype != torch.int32:
-        raise ValueError(f"{name}: cache_seqlens must be int32, got "
-                         f"{cache_seqlens.dtype}")
-    if cache_seqlens.shape != (B,):
-        raise ValueError(f"{name}: cache_seqlens must be [B] = [{B}], got "
-                         f"{tuple(cache_seqlens.shape)}")
-    if cache_seqlens.device != q.device:
-        raise ValueError(f"{name}: cache_seqlens is on "
-                         f"{cache_seqlens.device}, the inputs on {q.device}")
+    for n, t in (("cache_seqlens", cache_seqlens), ("q_lens", q_lens)):
+        if t is None and n == "q_lens":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: {n} must be a tensor")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name}: {n} must be int32, got {t.dtype}")
+        if t.shape != (B,):
+            raise ValueError(f"{name}: {n} must be [B] = [{B}], got "
+                             f"{tuple(t.shape)}")
+        if t.device != q.device:
+            raise ValueError(f"{name}: {n} is on {t.device}, the inputs on "
+                             f"{q.device}")
     if (k_new is None) != (v_new is None):
         raise ValueError(f"{name}: pass k_new and v_new together or neither")
+    want = (B, Hk) + tuple(q.shape[2:])
     for n, t in (("k_new", k_new), ("v_new", v_new)):
         if t is None:
             continue
-        if (t.shape != (B, Hk, D) or t.dtype != q.dtype
-                or t.device != q.device):
-            raise ValueError(f"{name}: {n} must be [B,Hk,D] = "
-                             f"[{B},{Hk},{D}] of q's dtype and device, got "
+        if t.shape != want or t.dtype != q.dtype or t.device != q.device:
+            raise ValueError(f"{name}: {n} must be [B,Hk,{rows}D] = "
+                             f"{list(want)} of q's dtype and device, got "
                              f"{tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+def _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new) -> None:
+    _check_cached("flash_attention_decode", q, k_cache, v_cache,
+                  cache_seqlens, k_new, v_new)
+
+
+def _check_no_grad(name, *tensors) -> None:
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name}: forward only, but an input requires "
+                           "grad; call it under torch.no_grad()")
 
 
 def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
@@ -869,12 +900,8 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
     key splits, an integer asks for that many (the kernels only). Anything
     else is composed from index_put and torch SDPA. Forward only."""
     _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new)
-    if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad
-            for t in (q, k_cache, v_cache, k_new, v_new)):
-        raise RuntimeError("flash_attention_decode: forward only, but an "
-                           "input requires grad; call it under "
-                           "torch.no_grad()")
+    _check_no_grad("flash_attention_decode", q, k_cache, v_cache, k_new,
+                   v_new)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("flash_attention_decode: num_splits must be None or "
                          f">= 1, got {num_splits}")
@@ -884,3 +911,167 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                               v_new, s, num_splits, return_lse)
     return _decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
                             scale, return_lse)
+
+
+# ---------------------------------------------------------------------------
+# Extend: a block of query rows per sequence against a KV cache
+# ---------------------------------------------------------------------------
+def _check_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                  q_lens) -> None:
+    _check_cached("flash_attention_extend", q, k_cache, v_cache,
+                  cache_seqlens, k_new, v_new, q_lens)
+
+
+def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
+                        v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
+                        q_lens: Optional[torch.Tensor] = None) -> bool:
+    """True where ``flash_attention_extend`` runs its kernels: bf16 on the
+    GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
+    contiguous and 16-B aligned, extension built."""
+    try:
+        _check_extend(q, k_cache, v_cache, cache_seqlens, None, None, q_lens)
+    except ValueError:
+        return False
+    return _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens)
+
+
+def _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens) -> bool:
+    """``fa_extend_supported`` for arguments ``_check_extend`` has passed."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16):
+        return False
+    if q.shape[3] not in (64, 128):
+        return False
+    if q.shape[1] // k_cache.shape[1] > _DECODE_MAX_GROUP:
+        return False
+    if not (_row_ok(q) and _row_ok(k_cache) and _row_ok(v_cache)):
+        return False
+    if not cache_seqlens.is_contiguous():
+        return False
+    if q_lens is not None and not q_lens.is_contiguous():
+        return False
+    return bool(_core())
+
+
+def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
+                   causal, scale, return_lse):
+    """The kernel path, for arguments that passed ``_check_extend`` and
+    ``_extend_kernel_ok``."""
+    B, H, Sq, D = q.shape
+    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
+    # [B,Sq,H,D] memory, as the forward's: transpose(1,2).view(B,Sq,C) is free
+    out = torch.empty((B, Sq, H, D), dtype=q.dtype,
+                      device=q.device).transpose(1, 2)
+    lse = (torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+           if return_lse else None)
+    kw = {}
+    new_strides = [0] * 6
+    if k_new is not None:
+        k_new = k_new if _row_ok(k_new) else k_new.contiguous()
+        v_new = v_new if _row_ok(v_new) else v_new.contiguous()
+        kw.update(k_new=k_new.data_ptr(), v_new=v_new.data_ptr())
+        new_strides = _strides3(k_new) + _strides3(v_new)
+    if q_lens is not None:
+        kw.update(q_lens=q_lens.data_ptr())
+    strides = (_strides3(q) + _strides3(k_cache) + _strides3(v_cache)
+               + _strides3(out) + new_strides)
+    with torch.cuda.device(q.device):   # the launch goes to q's device
+        stream = torch.cuda.current_stream().cuda_stream
+        _core().fa_extend(q.data_ptr(), k_cache.data_ptr(),
+                          v_cache.data_ptr(), cache_seqlens.data_ptr(),
+                          out.data_ptr(), B, H, Hk, Sq, Smax, D, strides,
+                          scale, bool(causal), stream,
+                          lse=lse.data_ptr() if return_lse else 0, **kw)
+    return (out, lse) if return_lse else out
+
+
+def _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
+                     causal, scale, return_lse):
+    """The append as one gathered, masked rewrite of the caches in place (an
+    index_put without duplicate targets), then SDPA under the explicit
+    [B,1,Sq,Smax] mask; no host sync."""
+    B, H, Sq, D = q.shape
+    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
+    dev = q.device
+    past = cache_seqlens.clamp(0, Smax).view(B, 1, 1, 1)
+    n = (torch.full_like(cache_seqlens, Sq) if q_lens is None
+         else q_lens.clamp(0, Sq)).view(B, 1, 1, 1)
+    keys = torch.arange(Smax, device=dev).view(1, 1, 1, Smax)
+    total = past
+    if k_new is not None:
+        # cache row j takes new row j - past_b where that is one of the n_b
+        src = keys.view(1, 1, Smax, 1) - past
+        hit = (src >= 0) & (src < n)
+        at = src.clamp(0, Sq - 1).long().expand(B, Hk, Smax, D)
+        k_cache.copy_(torch.where(hit, k_new.gather(2, at), k_cache))
+        v_cache.copy_(torch.where(hit, v_new.gather(2, at), v_cache))
+        total = (past + n).clamp(max=Smax)
+    rows = torch.arange(Sq, device=dev).view(1, 1, Sq, 1)
+    limit = total - n + rows if causal else (total - 1).expand(B, 1, Sq, 1)
+    mask = (rows < n) & (keys <= limit)                   # [B,1,Sq,Smax]
+    some = mask.any(-1, keepdim=True)                     # [B,1,Sq,1]
+    # rows past a sequence's length may hold anything, NaN included
+    live = (keys < total).view(B, 1, Smax, 1)
+    kz = torch.where(live, k_cache, 0)
+    vz = torch.where(live, v_cache, 0)
+    qz = torch.where(rows < n, q, 0)
+    gqa = {"enable_gqa": True} if Hk != H else {}
+    # an all-masked row would be NaN: let it see all keys, zero it afterwards
+    y = torch.nn.functional.scaled_dot_product_attention(
+        qz, kz, vz, attn_mask=mask | ~some, scale=scale, **gqa)
+    y = torch.where(some, y, 0)
+    y = y.transpose(1, 2).contiguous().transpose(1, 2)    # [B,Sq,H,D] memory
+    if not return_lse:
+        return y
+    s = scale if scale is not None else 1.0 / math.sqrt(D)
+    G = H // Hk
+    sc = torch.einsum("bhgqd,bhkd->bhgqk",
+                      qz.float().view(B, Hk, G, Sq, D), kz.float()) * s
+    sc = sc.masked_fill(~mask.unsqueeze(2), float("-inf"))
+    return y, torch.logsumexp(sc, dim=-1).view(B, H, Sq)
+
+
+def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
+                           v_cache: torch.Tensor,
+                           cache_seqlens: torch.Tensor,
+                           k_new: Optional[torch.Tensor] = None,
+                           v_new: Optional[torch.Tensor] = None,
+                           q_lens: Optional[torch.Tensor] = None,
+                           causal: bool = True, scale: float = None,
+                           return_lse: bool = False):
+    """Attention of a block of Sq query rows per sequence over a KV cache:
+    chunked prefill, a further turn on a kept cache, a few drafted tokens,
+    or (non-causal, no new rows) cross-attention. q: [B,H,Sq,D]; k_cache,
+    v_cache: [B,Hk,Smax,D] with H % Hk == 0 and any batch, head and row
+    strides (a [B,Smax,Hk,D] cache goes in as its transposed view), query
+    head h reading K/V head h // (H // Hk); cache_seqlens: int32 [B] on the
+    same device; q_lens: optional int32 [B], the number of leading query
+    rows of each sequence that are real. Returns [B,H,Sq,D] in [B,Sq,H,D]
+    memory, with ``return_lse`` also the fp32 [B,H,Sq] natural-log logsumexp
+    of the scaled scores.
+
+    past_b = clamp(cache_seqlens[b], 0, Smax); n_b = Sq, or clamp(q_lens[b],
+    0, Sq). With k_new and v_new ([B,Hk,Sq,D], both or neither, strided views
+    allowed) rows i < n_b are first written into cache rows past_b + i, in
+    place; rows that would land at or past Smax are dropped (the caller's
+    error: unspecified values, but no access outside the tensors), and
+    total_b = min(past_b + n_b, Smax). Without them total_b = past_b: the
+    caller has written and counted the chunk's keys already. With off_b =
+    total_b - n_b, query row i < n_b sees keys 0 .. off_b + i when causal
+    (bottom-right aligned) and keys < total_b when not. A row i >= n_b, or
+    one that sees no key, gives a zero row and lse -inf. Neither length
+    tensor is modified or read on the host, and no other cache row is
+    written. With Sq == 1, new rows and no q_lens this is
+    ``flash_attention_decode``.
+
+    bf16 on the GPU with D = 64 or 128 and H // Hk <= 32 runs the CDNA4
+    kernels of csrc/attn_extend.hip; anything else is composed from a masked
+    cache rewrite and torch SDPA under the explicit mask. Forward only."""
+    _check_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens)
+    _check_no_grad("flash_attention_extend", q, k_cache, v_cache, k_new,
+                   v_new)
+    if _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens):
+        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        return _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new,
+                              v_new, q_lens, causal, s, return_lse)
+    return _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                            q_lens, causal, scale, return_lse)

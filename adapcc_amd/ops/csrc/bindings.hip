@@ -128,6 +128,11 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
                void* out, float* lse, float* o_part, float* lse_part, int B,
                int H, int Hk, int Smax, int head_dim, const long* strides,
                float scale, int n_splits, int device, hipStream_t stream);
+void fa_extend(const void* q, void* k_cache, void* v_cache,
+               const int* seqlens, const int* q_lens, const void* k_new,
+               const void* v_new, void* out, float* lse, int B, int H, int Hk,
+               int Sq, int Smax, int head_dim, const long* strides,
+               float scale, bool causal, hipStream_t stream);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -439,6 +444,35 @@ PYBIND11_MODULE(_core, m) {
         py::arg("strides"), py::arg("scale"), py::arg("n_splits"),
         py::arg("device"), py::arg("stream"), py::arg("k_new") = 0, py::arg("v_new") = 0,
         py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0);
+  // Multi-row attention over a KV cache (attn_extend.hip). q and out
+  // [B,H,Sq,head_dim], caches [B,Hk,Smax,head_dim], seqlens int32 [B] on the
+  // device, q_lens int32 [B] or 0, lse fp32 [B,H,Sq] or 0. strides: q,
+  // k_cache, v_cache, out, k_new, v_new, (b, h, row) each. k_new, v_new != 0:
+  // rows i < n_b are appended at seqlens[b] + i first. The stream belongs to
+  // the current device. Nothing reads the lengths on the host.
+  m.def("fa_extend",
+        [](uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+           uintptr_t seqlens, uintptr_t out, int B, int H, int Hk, int Sq,
+           int Smax, int head_dim, const std::vector<long>& strides,
+           float scale, bool causal, uintptr_t stream, uintptr_t q_lens,
+           uintptr_t k_new, uintptr_t v_new, uintptr_t lse) {
+          if (strides.size() != 18)
+            throw std::runtime_error("fa_extend: need 18 strides");
+          adapcc::fa_extend((const void*)q, (void*)k_cache, (void*)v_cache,
+                            (const int*)seqlens, (const int*)q_lens,
+                            (const void*)k_new, (const void*)v_new,
+                            (void*)out, (float*)lse, B, H, Hk, Sq, Smax,
+                            head_dim, strides.data(), scale, causal,
+                            reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seqlens"), py::arg("out"), py::arg("B"), py::arg("H"),
+        py::arg("Hk"), py::arg("Sq"), py::arg("Smax"), py::arg("head_dim"),
+        py::arg("strides"), py::arg("scale"), py::arg("causal"),
+        py::arg("stream"), py::arg("q_lens") = 0, py::arg("k_new") = 0,
+        py::arg("v_new") = 0, py::arg("lse") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

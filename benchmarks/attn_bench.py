@@ -1,7 +1,7 @@
 """Flash-attention kernel timing: hand-written CDNA4 kernels vs torch SDPA.
 
 Run on a GPU box:  python benchmarks/attn_bench.py
-                       [--shape gpt2|vit|gpt2-d128|vit-d128|varlen|decode]
+                       [--shape gpt2|vit|gpt2-d128|vit-d128|varlen|decode|extend]
                        [--dropout P] [--head-dim 64|128] [--kv-heads N]
 
 gpt2 (default): B64 H12 S1024 D64, causal. vit: B64 H12 S197 D64, non-causal
@@ -32,6 +32,20 @@ the one-row query (which, its kernels being self-attention only, resolves to
 SDPA without a mask on the cache cut to the common length), and prints microseconds and the K/V bytes per second,
 2 * B * Hk * len * D * 2 bytes over the time. --sweep adds forced split
 counts, the measurement behind the split policy's constants.
+extend: a block of Sq query rows per sequence over a KV cache, causal, with
+the same heads as decode: pure prefill (B8, Sq 1024 and 1000, empty cache),
+chunked prefill (B8, Sq 512 over 3584 cached keys) and short chunks (B32 and
+B1, Sq 8 over 4096 and 16384). Times, alternating in one process,
+flash_attention_extend on a cache that already holds the chunk's keys, the
+same call appending them itself, the composed route on the same cache (torch
+SDPA under the explicit [B,1,Sq,Smax] mask with enable_gqa: the only route
+for these calls before the kernel), and, where the old prefill applies
+(empty cache, Sq % 128 == 0), flash_attention(causal=True) on q, k_new,
+v_new plus the two zero-filled cache copies that prefill made, and that
+forward alone. Prints the
+time with the spread of the rounds and the achieved FLOP/s (4 * B * H * D *
+visible (row, key) pairs) or, for the short chunks, K/V bytes per second,
+and for those the workgroup count against the CUs.
 """
 import argparse
 import math
@@ -67,7 +81,8 @@ def main():
     from adapcc_amd.ops.attention import fa_supported, flash_attention
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", choices=sorted(SHAPES) + ["varlen", "decode"],
+    ap.add_argument("--shape", choices=sorted(SHAPES) + ["varlen", "decode",
+                                                       "extend"],
                     default="gpt2")
     ap.add_argument("--sweep", action="store_true",
                     help="decode only: also time forced split counts")
@@ -85,6 +100,8 @@ def main():
     drop = args.dropout
     if args.shape == "decode":
         return decode_path(args.head_dim, args.kv_heads, args.sweep)
+    if args.shape == "extend":
+        return extend_path(args.head_dim, args.kv_heads)
     if args.shape == "varlen":
         H = 12 * 64 // args.head_dim
         if args.kv_heads:
@@ -232,6 +249,73 @@ def decode_path(D, kv_heads, sweep):
                           f"{nbytes / ms / 1e9:6.2f} TB/s  "
                           f"this/decode {ms / base:.2f}")
                 del q, k, v, mask, ref
+
+
+def extend_path(D, kv_heads):
+    from adapcc_amd.ops.attention import (_extend_composed,
+                                          fa_extend_supported, fa_supported,
+                                          flash_attention,
+                                          flash_attention_extend)
+
+    H = 16 if D == 128 else 12
+    kv = [kv_heads] if kv_heads else ([16, 4, 1] if D == 128 else [12, 1])
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+    for B, Sq, past in ((8, 1024, 0), (8, 1000, 0), (8, 512, 3584),
+                        (32, 8, 4096), (32, 8, 16384), (1, 8, 4096),
+                        (1, 8, 16384)):
+        for Hk in kv:
+            torch.manual_seed(0)
+            Smax = past + Sq
+            q = torch.randn(B, H, Sq, D, **bf)
+            k = torch.randn(B, Hk, Smax, D, **bf)
+            v = torch.randn_like(k)
+            kn = k[:, :, past:].clone()
+            vn = v[:, :, past:].clone()
+            lens0 = torch.full((B,), past, dtype=torch.int32, device="cuda")
+            lens1 = lens0 + Sq
+            # a missing kernel is an error, not a silent SDPA-vs-SDPA run
+            assert fa_extend_supported(q, k, v, lens0)
+            fns = {
+                "extend": lambda: flash_attention_extend(q, k, v, lens1),
+                "extend + append": lambda: flash_attention_extend(
+                    q, k, v, lens0, kn, vn),
+                "composed sdpa mask": lambda: _extend_composed(
+                    q, k, v, lens1, None, None, None, True, None, False),
+            }
+            if past == 0 and Sq % 128 == 0:
+                assert fa_supported(q, kn, vn, True, 0.0)
+
+                def old_prefill():
+                    for t in (kn, vn):
+                        c = t.new_zeros(B, Smax, Hk, D)
+                        c[:, :Sq] = t.transpose(1, 2)
+                    return flash_attention(q, kn, vn, causal=True)
+
+                fns["forward + 2 cache copies"] = old_prefill
+                fns["forward alone"] = lambda: flash_attention(
+                    q, kn, vn, causal=True)
+            want = _extend_composed(q.float(), k.float(), v.float(), lens1,
+                                    None, None, None, True, None, False)
+            err = (fns["extend"]().float() - want).abs().max().item()
+            pairs = Sq * past + Sq * (Sq + 1) // 2
+            flops = 4 * B * H * D * pairs
+            nbytes = 2 * B * Hk * Smax * D * 2
+            short = Sq < 128
+            wgs = B * Hk * -(-Sq * (H // Hk) // 128)
+            print(f"B{B} H{H} Hk{Hk} D{D} Sq{Sq} past{past}  "
+                  f"({flops / 1e9:.1f} GFLOP, K/V {nbytes / 2**20:.1f} MiB, "
+                  f"{wgs} workgroups on {n_cu} CUs, max err vs fp32 "
+                  f"{err:.2e})")
+            base = None
+            for name, (ms, lo, hi) in alternate(fns, window=0.3).items():
+                base = base or ms
+                rate = (f"{nbytes / ms / 1e9:6.2f} TB/s" if short
+                        else f"{flops / ms / 1e9:7.1f} TF/s")
+                print(f"  {name:<26} {ms * 1e3:9.1f} us  (rounds "
+                      f"{lo * 1e3:.1f}..{hi * 1e3:.1f})  {rate}  "
+                      f"this/extend {ms / base:.2f}")
+            del q, k, v, kn, vn, want
 
 
 def report(title, res, flops):
