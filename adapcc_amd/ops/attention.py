@@ -52,8 +52,7 @@ for all H // Hk query heads, and merge the splits deterministically. The
 split count depends on the shapes alone, so there is no host sync either and
 a captured graph whose lengths are refilled stays valid. With ``k_new`` and
 ``v_new`` the new token's rows are first written into the cache in place.
-Forward only. Off the kernel path it is composed from ``index_put`` and
-torch SDPA under a key-length mask.
+Forward only.
 
 ``flash_attention_extend`` is the same over a block of rows: q [B,H,Sq,D]
 against the cache, optionally appending the block's own k and v rows
@@ -66,12 +65,18 @@ head) axis, so a K/V tile is staged once for all H // Hk heads and a short
 chunk under GQA still fills its MFMA columns. No host sync; forward only. A
 short chunk over a long cache is not split over the keys, so it leaves most
 of the chip idle.
+
+Decode is extend at Sq = 1 with new rows and no ``q_lens``, so the two share
+their host path: ``_check_cached``, ``_cached_kernel_ok``, the launch preamble
+``_cached_launch_args``, one append kernel (csrc/attn_cache.h) and, off the
+kernel path, ``_extend_composed`` (a masked rewrite of the caches, then torch
+SDPA under the explicit mask), which decode calls on ``unsqueeze(2)`` views.
 """
 
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -105,12 +110,14 @@ def _bhsd(t: torch.Tensor) -> torch.Tensor:
 
 
 def _row_ok(t: torch.Tensor) -> bool:
-    if t.stride(3) != 1:
+    """Rows (the last dimension) contiguous and 16-B aligned, whatever the
+    number of leading dimensions."""
+    if t.stride(-1) != 1:
         return False
     if t.data_ptr() % 16 != 0:
         return False
     # every row/plane base must stay 16-B aligned (bf16: 8 elements)
-    return all(s % 8 == 0 for s in _strides3(t))
+    return all(s % 8 == 0 for s in t.stride()[:-1])
 
 
 def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
@@ -691,17 +698,10 @@ def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
 
 
 # ---------------------------------------------------------------------------
-# Decode: one query row per sequence against a KV cache
+# Attention over a KV cache: what decode (one query row per sequence) and
+# extend (a block of rows) share
 # ---------------------------------------------------------------------------
 _DECODE_MAX_GROUP = 32  # csrc/attn_decode_plan.h's kDecodeMaxGroup
-
-
-def _rows_ok(t: torch.Tensor) -> bool:
-    """Rows (the last dimension) contiguous and 16-B aligned, whatever the
-    number of leading dimensions: ``_row_ok`` for q and k_new too."""
-    if t.stride(-1) != 1 or t.data_ptr() % 16 != 0:
-        return False
-    return all(s % 8 == 0 for s in t.stride()[:-1])
 
 
 def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
@@ -754,11 +754,6 @@ def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
                              f"{tuple(t.shape)} {t.dtype} on {t.device}")
 
 
-def _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new) -> None:
-    _check_cached("flash_attention_decode", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new)
-
-
 def _check_no_grad(name, *tensors) -> None:
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in tensors):
@@ -766,6 +761,59 @@ def _check_no_grad(name, *tensors) -> None:
                            "grad; call it under torch.no_grad()")
 
 
+def _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens,
+                      q_lens=None) -> bool:
+    """Where the cached calls run their kernels, for arguments that
+    ``_check_cached`` has passed."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16):
+        return False
+    if q.shape[-1] not in (64, 128):
+        return False
+    if q.shape[1] // k_cache.shape[1] > _DECODE_MAX_GROUP:
+        return False
+    if not (_row_ok(q) and _row_ok(k_cache) and _row_ok(v_cache)):
+        return False
+    if not cache_seqlens.is_contiguous():
+        return False
+    if q_lens is not None and not q_lens.is_contiguous():
+        return False
+    return bool(_core())
+
+
+class _CachedLaunch(NamedTuple):
+    """What both kernel launches over a cache build the same way."""
+    kw: dict            # pointers: k_new, v_new (with new rows), lse (asked for)
+    new_strides: list   # of the new rows, k's then v's; zeros without them
+    lse: Optional[torch.Tensor]     # fp32, q's shape without D, or None
+    device: int         # q's index: the launchers make it current
+    stream: int         # that device's current stream
+    # the tensors kw's k_new, v_new point into (contiguous copies of rows not
+    # 16-B aligned): alive while the launcher holds this result
+    new_rows: Optional[tuple]
+
+
+def _cached_launch_args(q, k_new, v_new, return_lse) -> _CachedLaunch:
+    kw = {}
+    new_rows = None
+    new_strides = [0] * (2 * (q.dim() - 1))
+    if k_new is not None:
+        new_rows = tuple(t if _row_ok(t) else t.contiguous()
+                         for t in (k_new, v_new))
+        kw.update(k_new=new_rows[0].data_ptr(), v_new=new_rows[1].data_ptr())
+        new_strides = list(new_rows[0].stride()[:-1]
+                           + new_rows[1].stride()[:-1])
+    lse = None
+    if return_lse:
+        lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+        kw.update(lse=lse.data_ptr())
+    return _CachedLaunch(kw, new_strides, lse, q.get_device(),
+                         torch.cuda.current_stream(q.device).cuda_stream,
+                         new_rows)
+
+
+# ---------------------------------------------------------------------------
+# Decode: one query row per sequence against a KV cache
+# ---------------------------------------------------------------------------
 def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor,
                         cache_seqlens: torch.Tensor) -> bool:
@@ -773,101 +821,37 @@ def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
     contiguous and 16-B aligned, extension built."""
     try:
-        _check_decode(q, k_cache, v_cache, cache_seqlens, None, None)
+        _check_cached("flash_attention_decode", q, k_cache, v_cache,
+                      cache_seqlens, None, None)
     except ValueError:
         return False
-    return _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens)
-
-
-def _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens) -> bool:
-    """``fa_decode_supported`` for arguments ``_check_decode`` has passed."""
-    if not (q.is_cuda and q.dtype == torch.bfloat16):
-        return False
-    if q.shape[2] not in (64, 128):
-        return False
-    if q.shape[1] // k_cache.shape[1] > _DECODE_MAX_GROUP:
-        return False
-    if not (_rows_ok(q) and _row_ok(k_cache) and _row_ok(v_cache)):
-        return False
-    if not cache_seqlens.is_contiguous():
-        return False
-    return bool(_core())
+    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens)
 
 
 def _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
                    num_splits, return_lse):
-    """The kernel path, for arguments that passed ``_check_decode`` and
-    ``_decode_kernel_ok``."""
+    """The kernel path, for arguments that passed ``_check_cached`` and
+    ``_cached_kernel_ok``."""
     core = _core()
     B, H, D = q.shape
     Hk, Smax = k_cache.shape[1], k_cache.shape[2]
-    dev = q.get_device()  # the launcher makes it current for the call
+    a = _cached_launch_args(q, k_new, v_new, return_lse)
     ns = core.fa_decode_splits(B, Hk, Smax,
                                0 if num_splits is None else int(num_splits),
-                               dev)
+                               a.device)
     out = torch.empty((B, H, D), dtype=q.dtype, device=q.device)
-    lse = (torch.empty((B, H), dtype=torch.float32, device=q.device)
-           if return_lse else None)
-    kw = {}
     if ns > 1:
         o_part = torch.empty((B, H, ns, D), dtype=torch.float32,
                              device=q.device)
         lse_part = torch.empty((B, H, ns), dtype=torch.float32,
                                device=q.device)
-        kw.update(o_part=o_part.data_ptr(), lse_part=lse_part.data_ptr())
-    new_strides = [0, 0, 0, 0]
-    if k_new is not None:
-        k_new = k_new if _rows_ok(k_new) else k_new.contiguous()
-        v_new = v_new if _rows_ok(v_new) else v_new.contiguous()
-        kw.update(k_new=k_new.data_ptr(), v_new=v_new.data_ptr())
-        new_strides = [k_new.stride(0), k_new.stride(1), v_new.stride(0),
-                       v_new.stride(1)]
+        a.kw.update(o_part=o_part.data_ptr(), lse_part=lse_part.data_ptr())
     strides = ([q.stride(0), q.stride(1)] + _strides3(k_cache)
-               + _strides3(v_cache) + new_strides)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
+               + _strides3(v_cache) + a.new_strides)
     core.fa_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                    cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Smax,
-                   D, strides, scale, ns, dev, stream,
-                   lse=lse.data_ptr() if return_lse else 0, **kw)
-    return (out, lse) if return_lse else out
-
-
-def _decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
-                     return_lse):
-    """index_put for the append, then SDPA under the [B,1,1,Smax] key-length
-    mask; no host sync. A sequence with no key gives a zero row."""
-    B, H, D = q.shape
-    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
-    lens = cache_seqlens.clamp(0, Smax)
-    if k_new is not None:
-        # a full cache is left alone: index Smax - 1 gets its own old row
-        room = (lens < Smax).view(B, 1, 1)
-        at = lens.clamp(max=Smax - 1).long()
-        rows = torch.arange(B, device=q.device)
-        # indexed assignment is index_put_
-        k_cache[rows, :, at] = torch.where(room, k_new, k_cache[rows, :, at])
-        v_cache[rows, :, at] = torch.where(room, v_new, v_cache[rows, :, at])
-        lens = (lens + 1).clamp(max=Smax)
-    keys = torch.arange(Smax, device=q.device).view(1, 1, 1, Smax)
-    mask = keys < lens.view(B, 1, 1, 1)
-    some = (lens > 0).view(B, 1, 1)
-    # rows past a sequence's length may hold anything, NaN included
-    kz = torch.where(mask.view(B, 1, Smax, 1), k_cache, 0)
-    vz = torch.where(mask.view(B, 1, Smax, 1), v_cache, 0)
-    gqa = {"enable_gqa": True} if Hk != H else {}
-    # an all-masked row would be NaN: let it see key 0, zero it afterwards
-    y = torch.nn.functional.scaled_dot_product_attention(
-        q.unsqueeze(2), kz, vz, attn_mask=mask | ~some.view(B, 1, 1, 1),
-        scale=scale, **gqa).squeeze(2)
-    y = torch.where(some, y, 0)
-    if not return_lse:
-        return y
-    s = scale if scale is not None else 1.0 / math.sqrt(D)
-    G = H // Hk
-    sc = torch.einsum("bhgd,bhkd->bhgk", q.float().view(B, Hk, G, D),
-                      kz.float()) * s
-    sc = sc.masked_fill(~mask, float("-inf"))
-    return y, torch.logsumexp(sc, dim=-1).view(B, H)
+                   D, strides, scale, ns, a.device, a.stream, **a.kw)
+    return (out, a.lse) if return_lse else out
 
 
 def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
@@ -898,30 +882,29 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
     bf16 on the GPU with D = 64 or 128 and H // Hk <= 32 runs the CDNA4
     split-KV kernels; num_splits None lets the shapes decide the number of
     key splits, an integer asks for that many (the kernels only). Anything
-    else is composed from index_put and torch SDPA. Forward only."""
-    _check_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new)
+    else is composed as ``flash_attention_extend`` composes a block of one
+    row. Forward only."""
+    _check_cached("flash_attention_decode", q, k_cache, v_cache,
+                  cache_seqlens, k_new, v_new)
     _check_no_grad("flash_attention_decode", q, k_cache, v_cache, k_new,
                    v_new)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("flash_attention_decode: num_splits must be None or "
                          f">= 1, got {num_splits}")
-    if _decode_kernel_ok(q, k_cache, v_cache, cache_seqlens):
+    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new,
                               v_new, s, num_splits, return_lse)
-    return _decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                            scale, return_lse)
+    # a block of one row; [B,1,H,D] memory, so the [B,H,D] result is contiguous
+    one = [None if t is None else t.unsqueeze(2) for t in (q, k_new, v_new)]
+    res = _extend_composed(one[0], k_cache, v_cache, cache_seqlens, one[1],
+                           one[2], None, True, scale, return_lse)
+    return (res[0][:, :, 0], res[1][:, :, 0]) if return_lse else res[:, :, 0]
 
 
 # ---------------------------------------------------------------------------
 # Extend: a block of query rows per sequence against a KV cache
 # ---------------------------------------------------------------------------
-def _check_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                  q_lens) -> None:
-    _check_cached("flash_attention_extend", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new, q_lens)
-
-
 def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
                         q_lens: Optional[torch.Tensor] = None) -> bool:
@@ -929,59 +912,32 @@ def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
     contiguous and 16-B aligned, extension built."""
     try:
-        _check_extend(q, k_cache, v_cache, cache_seqlens, None, None, q_lens)
+        _check_cached("flash_attention_extend", q, k_cache, v_cache,
+                      cache_seqlens, None, None, q_lens)
     except ValueError:
         return False
-    return _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens)
-
-
-def _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens) -> bool:
-    """``fa_extend_supported`` for arguments ``_check_extend`` has passed."""
-    if not (q.is_cuda and q.dtype == torch.bfloat16):
-        return False
-    if q.shape[3] not in (64, 128):
-        return False
-    if q.shape[1] // k_cache.shape[1] > _DECODE_MAX_GROUP:
-        return False
-    if not (_row_ok(q) and _row_ok(k_cache) and _row_ok(v_cache)):
-        return False
-    if not cache_seqlens.is_contiguous():
-        return False
-    if q_lens is not None and not q_lens.is_contiguous():
-        return False
-    return bool(_core())
+    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens)
 
 
 def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
                    causal, scale, return_lse):
-    """The kernel path, for arguments that passed ``_check_extend`` and
-    ``_extend_kernel_ok``."""
+    """The kernel path, for arguments that passed ``_check_cached`` and
+    ``_cached_kernel_ok``."""
     B, H, Sq, D = q.shape
     Hk, Smax = k_cache.shape[1], k_cache.shape[2]
+    a = _cached_launch_args(q, k_new, v_new, return_lse)
     # [B,Sq,H,D] memory, as the forward's: transpose(1,2).view(B,Sq,C) is free
     out = torch.empty((B, Sq, H, D), dtype=q.dtype,
                       device=q.device).transpose(1, 2)
-    lse = (torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-           if return_lse else None)
-    kw = {}
-    new_strides = [0] * 6
-    if k_new is not None:
-        k_new = k_new if _row_ok(k_new) else k_new.contiguous()
-        v_new = v_new if _row_ok(v_new) else v_new.contiguous()
-        kw.update(k_new=k_new.data_ptr(), v_new=v_new.data_ptr())
-        new_strides = _strides3(k_new) + _strides3(v_new)
     if q_lens is not None:
-        kw.update(q_lens=q_lens.data_ptr())
+        a.kw.update(q_lens=q_lens.data_ptr())
     strides = (_strides3(q) + _strides3(k_cache) + _strides3(v_cache)
-               + _strides3(out) + new_strides)
-    with torch.cuda.device(q.device):   # the launch goes to q's device
-        stream = torch.cuda.current_stream().cuda_stream
-        _core().fa_extend(q.data_ptr(), k_cache.data_ptr(),
-                          v_cache.data_ptr(), cache_seqlens.data_ptr(),
-                          out.data_ptr(), B, H, Hk, Sq, Smax, D, strides,
-                          scale, bool(causal), stream,
-                          lse=lse.data_ptr() if return_lse else 0, **kw)
-    return (out, lse) if return_lse else out
+               + _strides3(out) + a.new_strides)
+    _core().fa_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                      cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Sq,
+                      Smax, D, strides, scale, bool(causal), a.device,
+                      a.stream, **a.kw)
+    return (out, a.lse) if return_lse else out
 
 
 def _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
@@ -1066,10 +1022,11 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
     bf16 on the GPU with D = 64 or 128 and H // Hk <= 32 runs the CDNA4
     kernels of csrc/attn_extend.hip; anything else is composed from a masked
     cache rewrite and torch SDPA under the explicit mask. Forward only."""
-    _check_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens)
+    _check_cached("flash_attention_extend", q, k_cache, v_cache,
+                  cache_seqlens, k_new, v_new, q_lens)
     _check_no_grad("flash_attention_extend", q, k_cache, v_cache, k_new,
                    v_new)
-    if _extend_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens):
+    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new,
                               v_new, q_lens, causal, s, return_lse)

@@ -1,0 +1,185 @@
+// What the two attention kernels over a KV cache share (gfx950, bf16):
+// attn_decode.hip (one query row per sequence, split over the keys) and
+// attn_extend.hip (a block of rows): the clamped lengths of a sequence, the
+// cache append's interface (one kernel, in attn_extend.hip), the host
+// helpers that make the tensors' device current, and cache_tile_step, the
+// span from the finished score tile to the last PV MFMA. Decode calls it;
+// extend holds the same span written out (with an s_setprio pair), since as
+// a function call it got another register allocation and lost time at one
+// shape (profiles/README.md, "Shared header ..."). Compiled only through the
+// two files, so with their flags (ops/build.py: packed fp32 VALU forms off).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdexcept>
+#include <string>
+
+#include "attn_frag.h"
+
+namespace adapcc {
+
+constexpr float kNegBig = -3.0e38f;
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+
+// The lengths of sequence b: past_b = clamp(seqlens[b], 0, Smax) cached keys,
+// n_b = clamp(q_lens[b], 0, Sq) new rows (Sq without q_lens), total_b the
+// keys that count, with the new rows where they were appended. The clamps
+// bound every address the kernels form: a malformed length cannot send a
+// load or store outside the tensors.
+struct SeqLens {
+  int past, n, total;
+};
+
+__device__ __forceinline__ SeqLens seq_lens(const int* seqlens,
+                                            const int* q_lens, int b, int Sq,
+                                            int Smax, int append) {
+  SeqLens s;
+  s.past = min(max(seqlens[b], 0), Smax);
+  s.n = q_lens != nullptr ? min(max(q_lens[b], 0), Sq) : Sq;
+  s.total = append ? min(s.past + s.n, Smax) : s.past;
+  return s;
+}
+
+// Four f32 -> four bf16 (round to nearest even), one 8-byte store.
+__device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
+                                            float c, float d) {
+  unsigned lo, hi;
+  asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
+      "v_cvt_pk_bf16_f32 %1, %4, %5"
+      : "=&v"(lo), "=&v"(hi)
+      : "v"(a), "v"(b), "v"(c), "v"(d));
+  uint2 st = {lo, hi};
+  *reinterpret_cast<uint2*>(dst) = st;
+}
+
+// One 32-key tile of the online softmax and of O^T += V^T · P^T. `s` is the
+// finished S^T tile (this lane: keys kbase + crow(r, lane >> 5) of its own
+// row). `masked` is wave-uniform: the tile reaches past some lane's `lim`,
+// the last key that lane sees, and keys past it go to kNegBig before the
+// running max. `vimg` is the tile's V as attn_frag.h row images, one per 64
+// columns, `vblk` bytes apart. m, mc = m * c1, ssum: the lane's running max
+// and row sum, c1 = scale * log2(e). acc0..acc3 are O^T, one per 32 columns
+// (acc2, acc3 dead at head_dim 64); named, not an array: an array went to
+// scratch.
+//
+// A row that has seen no key yet holds m = kNegBig and gets P = 1 here:
+// finite, lane-local, and for its caller to throw away.
+template <int kHD>
+__device__ __forceinline__ void cache_tile_step(
+    const f32x16& s, bool masked, int kbase, int lim, const char* vimg,
+    int vblk, int lane, float& m, float& mc, float& ssum, float c1,
+    f32x16& acc0, f32x16& acc1, f32x16& acc2, f32x16& acc3) {
+  const int hi = lane >> 5;
+  float pv[16];
+  float tmax = kNegBig;
+  if (masked) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      pv[r] = kbase + crow(r, hi) > lim ? kNegBig : s[r];
+      tmax = fmaxf(tmax, pv[r]);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      pv[r] = s[r];
+      tmax = fmaxf(tmax, pv[r]);
+    }
+  }
+  tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+  if (!__all(tmax <= m)) {
+    const float mnew = fmaxf(m, tmax);
+    const float alpha = __builtin_amdgcn_exp2f((m - mnew) * c1);
+    m = mnew;
+    mc = m * c1;
+    ssum *= alpha;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc0[r] *= alpha;
+      acc1[r] *= alpha;
+      if constexpr (kHD == 128) {
+        acc2[r] *= alpha;
+        acc3[r] *= alpha;
+      }
+    }
+  }
+
+  float psum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(pv[r], c1, -mc));
+    psum += pv[r];
+  }
+  ssum += psum;
+
+  // P to operand fragments (keys 0-15 / 16-31), then
+  // O^T += V^T · P^T with V^T from hardware transpose reads
+  const bf16x8 p0 = pack_frag(&pv[0]);
+  const bf16x8 p1 = pack_frag(&pv[8]);
+  acc0 = mfma(read_tr_frag(vimg, lane, 0, 0), p0, acc0);
+  acc0 = mfma(read_tr_frag(vimg, lane, 1, 0), p1, acc0);
+  acc1 = mfma(read_tr_frag(vimg, lane, 0, 1), p0, acc1);
+  acc1 = mfma(read_tr_frag(vimg, lane, 1, 1), p1, acc1);
+  if constexpr (kHD == 128) {
+    acc2 = mfma(read_tr_frag(vimg + vblk, lane, 0, 0), p0, acc2);
+    acc2 = mfma(read_tr_frag(vimg + vblk, lane, 1, 0), p1, acc2);
+    acc3 = mfma(read_tr_frag(vimg + vblk, lane, 0, 1), p0, acc3);
+    acc3 = mfma(read_tr_frag(vimg + vblk, lane, 1, 1), p1, acc3);
+  }
+}
+
+// In-place cache update ahead of the attention kernel, on its stream (defined
+// in attn_extend.hip): rows i < n_b of k_new, v_new [B, Hk, Sq, head_dim] go
+// to cache rows past_b + i; rows that would land at or past Smax are dropped,
+// so a full cache is left alone. cache_strides: k_cache, then v_cache, (b, h,
+// row) each; new_strides: k_new, then v_new, likewise. q_lens may be null.
+// The caller has checked the shapes and made the device current.
+void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
+                     const void* v_new, const int* seqlens, const int* q_lens,
+                     const long* cache_strides, const long* new_strides, int B,
+                     int Hk, int Sq, int Smax, int head_dim,
+                     hipStream_t stream);
+
+// Makes `device` HIP's current device for the scope of a host call, so the
+// launches (and decode's CU count) belong to the device the tensors and the
+// stream are on; puts the caller's device back afterwards. `name` opens the
+// error messages.
+class DeviceScope {
+ public:
+  DeviceScope(const char* name, int device) {
+    if (hipGetDevice(&prev_) != hipSuccess)
+      throw std::runtime_error(std::string(name) +
+                               ": cannot read the current device");
+    if (device != prev_) {
+      if (hipSetDevice(device) != hipSuccess)
+        throw std::runtime_error(std::string(name) +
+                                 ": cannot select device " +
+                                 std::to_string(device));
+      changed_ = true;
+    }
+  }
+  ~DeviceScope() {
+    if (changed_) (void)hipSetDevice(prev_);
+  }
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+
+ private:
+  int prev_ = 0;
+  bool changed_ = false;
+};
+
+// CUs of the current device, asked each time (no process-wide cache: hosts
+// can hold different devices).
+inline int device_cu_count(const char* name) {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
+                            dev) != hipSuccess || n < 1)
+    throw std::runtime_error(std::string(name) +
+                             ": cannot read the CU count");
+  return n;
+}
+
+}  // namespace adapcc

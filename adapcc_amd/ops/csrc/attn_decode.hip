@@ -43,9 +43,12 @@
 //    leaves before any barrier. fa_decode_combine_kernel, one wave per (b, h),
 //    merges them and rounds once to bf16. n_splits == 1: the decode kernel
 //    writes bf16 itself. No atomics, no counters: deterministic.
-//  * fa_decode_append_kernel copies the new token's k and v rows into cache
-//    row len_b ahead of the decode kernel on the same stream; attention then
-//    covers len_b + 1 keys. A full cache is left alone.
+//  * fa_cache_append (attn_cache.h; the one append kernel, at Sq = 1) copies
+//    the new token's k and v rows into cache row len_b ahead of the decode
+//    kernel on the same stream; attention then covers len_b + 1 keys. A full
+//    cache is left alone.
+//  * From the score tile to the last PV MFMA a sub-tile runs attn_cache.h's
+//    cache_tile_step (attn_extend.hip holds the same span written out).
 //
 // How a wave gets its K fragment (32 keys x 16 columns, 16 B of one key row
 // per lane): each lane loads its 16 B straight from global in fragment
@@ -96,7 +99,9 @@
 // which has not been run with them. Compile-time difference: with default
 // flags 60 v_pk_mul_f32 and 49 v_pk_fma_f32 (the accumulator rescale and
 // the merge), with the flag none; registers, LDS and scratch are the same.
-// Every figure in this header is of the build with the flag.
+// Every figure in this header is of the build with the flag, taken before
+// the tile step moved to attn_cache.h: resources and instruction counts are
+// the same since, operand order differs (profiles/README.md, "Shared header").
 
 #include <hip/hip_runtime.h>
 
@@ -105,6 +110,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "attn_cache.h"
 #include "attn_decode_plan.h"
 #include "attn_frag.h"
 
@@ -112,9 +118,6 @@ namespace adapcc {
 
 namespace {
 
-constexpr float kNegBig = -3.0e38f;
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kBlkImg = 4096;  // attn_frag.h's [32][64] bf16 row image
 
 struct DecodeParams {
@@ -131,13 +134,6 @@ struct DecodeParams {
   __bf16* out;              // [B, H, D] contiguous
   float* lse;               // [B, H], may be null
 };
-
-// Keys that count for sequence b. The clamp bounds every address below: a
-// malformed length cannot send a load or store outside the cache.
-__device__ __forceinline__ int cache_len(const int* seqlens, int b,
-                                         int Smax) {
-  return min(max(seqlens[b], 0), Smax);
-}
 
 // One wave's share of a [32 keys][kHD] sub-tile: per 64-column block, lane t
 // moves the 16 B at column (t&7)*8 of rows (t>>3) + 8*i, i = 0..3, so every
@@ -200,17 +196,6 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
-                                            float c, float d) {
-  unsigned lo, hi;
-  asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
-      "v_cvt_pk_bf16_f32 %1, %4, %5"
-      : "=&v"(lo), "=&v"(hi)
-      : "v"(a), "v"(b), "v"(c), "v"(d));
-  uint2 st = {lo, hi};
-  *reinterpret_cast<uint2*>(dst) = st;
-}
-
 // ---------------------------------------------------------------------------
 // Partial attention of one (batch, K/V head, key split).
 // Grid (n_splits, Hk, B), 256 threads = 4 waves.
@@ -235,8 +220,8 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
   const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const int G = p.G, H = p.H;
 
-  int len = cache_len(p.seqlens, b, p.Smax);
-  if (p.append) len = min(len + 1, p.Smax);
+  // the keys that count, the appended one among them; clamped to [0, Smax]
+  const int len = seq_lens(p.seqlens, nullptr, b, 1, p.Smax, p.append).total;
   const int k0 = split * p.L;
   const int kend = min(k0 + p.L, len);
 
@@ -307,62 +292,9 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
 #pragma unroll
     for (int c = 0; c < kNC; ++c) s = mfma(kf.f[c], qf[c], s);
 
-    float pv[16];
-    float tmax = kNegBig;
-    if (kb + 31 > klast) {
-      // the sub-tile that holds the split's last key: mask the rest
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        pv[r] = kb + crow(r, hi) > klast ? kNegBig : s[r];
-        tmax = fmaxf(tmax, pv[r]);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        pv[r] = s[r];
-        tmax = fmaxf(tmax, pv[r]);
-      }
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    if (!__all(tmax <= m)) {
-      const float mnew = fmaxf(m, tmax);
-      const float alpha = __builtin_amdgcn_exp2f((m - mnew) * c1);
-      m = mnew;
-      mc = m * c1;
-      ssum *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        acc0[r] *= alpha;
-        acc1[r] *= alpha;
-        if constexpr (kNB == 4) {
-          acc2[r] *= alpha;
-          acc3[r] *= alpha;
-        }
-      }
-    }
-
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(pv[r], c1, -mc));
-      psum += pv[r];
-    }
-    ssum += psum;
-
-    // P to operand fragments (keys 0-15 / 16-31), then
-    // O^T += V^T · P^T with V^T from hardware transpose reads
-    const bf16x8 p0 = pack_frag(&pv[0]);
-    const bf16x8 p1 = pack_frag(&pv[8]);
-    acc0 = mfma(read_tr_frag(vim, lane, 0, 0), p0, acc0);
-    acc0 = mfma(read_tr_frag(vim, lane, 1, 0), p1, acc0);
-    acc1 = mfma(read_tr_frag(vim, lane, 0, 1), p0, acc1);
-    acc1 = mfma(read_tr_frag(vim, lane, 1, 1), p1, acc1);
-    if constexpr (kNB == 4) {
-      acc2 = mfma(read_tr_frag(vim + kBlkImg, lane, 0, 0), p0, acc2);
-      acc2 = mfma(read_tr_frag(vim + kBlkImg, lane, 1, 0), p1, acc2);
-      acc3 = mfma(read_tr_frag(vim + kBlkImg, lane, 0, 1), p0, acc3);
-      acc3 = mfma(read_tr_frag(vim + kBlkImg, lane, 1, 1), p1, acc3);
-    }
+    // softmax and PV; the sub-tile with the split's last key masks the rest
+    cache_tile_step<kHD>(s, kb + 31 > klast, kb, klast, vim, kBlkImg, lane,
+                         m, mc, ssum, c1, acc0, acc1, acc2, acc3);
     wave_lds_fence();
   }
 
@@ -465,72 +397,6 @@ __global__ __launch_bounds__(64) void fa_decode_combine_kernel(
   if (lane == 0 && lse != nullptr) lse[bh] = tot;
 }
 
-// ---------------------------------------------------------------------------
-// In-place cache update: grid (Hk, B), 32 threads; thread t < D/8 copies 16 B
-// of the k row, the next D/8 threads the v row. A full cache (len >= Smax)
-// is left alone.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(32) void fa_decode_append_kernel(
-    __bf16* k_cache, __bf16* v_cache, const __bf16* k_new,
-    const __bf16* v_new, const int* seqlens, long k_sb, long k_sh, long k_ss,
-    long v_sb, long v_sh, long v_ss, long kn_sb, long kn_sh, long vn_sb,
-    long vn_sh, int Smax, int D) {
-  const int hk = blockIdx.x, b = blockIdx.y;
-  const int len = cache_len(seqlens, b, Smax);
-  if (len >= Smax) return;
-  const int per = D / 8;
-  const int t = threadIdx.x;
-  if (t >= 2 * per) return;
-  const int i = (t % per) * 8;
-  if (t < per)
-    *reinterpret_cast<uint4*>(k_cache + (long)b * k_sb + (long)hk * k_sh +
-                              (long)len * k_ss + i) =
-        *reinterpret_cast<const uint4*>(k_new + (long)b * kn_sb +
-                                        (long)hk * kn_sh + i);
-  else
-    *reinterpret_cast<uint4*>(v_cache + (long)b * v_sb + (long)hk * v_sh +
-                              (long)len * v_ss + i) =
-        *reinterpret_cast<const uint4*>(v_new + (long)b * vn_sb +
-                                        (long)hk * vn_sh + i);
-}
-
-// Makes `device` HIP's current device for the scope of a host call, so the
-// policy's CU count and the launches belong to the device the tensors (and
-// the stream) are on; puts the caller's device back afterwards.
-class DeviceScope {
- public:
-  explicit DeviceScope(int device) {
-    if (hipGetDevice(&prev_) != hipSuccess)
-      throw std::runtime_error("fa_decode: cannot read the current device");
-    if (device != prev_) {
-      if (hipSetDevice(device) != hipSuccess)
-        throw std::runtime_error("fa_decode: cannot select device " +
-                                 std::to_string(device));
-      changed_ = true;
-    }
-  }
-  ~DeviceScope() {
-    if (changed_) (void)hipSetDevice(prev_);
-  }
-  DeviceScope(const DeviceScope&) = delete;
-  DeviceScope& operator=(const DeviceScope&) = delete;
-
- private:
-  int prev_ = 0;
-  bool changed_ = false;
-};
-
-// CUs of the current device, asked each time (no process-wide cache: hosts
-// can hold different devices).
-int device_cu_count() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                            dev) != hipSuccess || n < 1)
-    throw std::runtime_error("fa_decode: cannot read the CU count");
-  return n;
-}
-
 template <int kHD>
 void launch_decode(const DecodeParams& p, dim3 grid, long BH,
                    hipStream_t stream) {
@@ -553,8 +419,9 @@ void launch_decode(const DecodeParams& p, dim3 grid, long BH,
 int fa_decode_splits(int B, int Hk, int Smax, int num_splits, int device) {
   if (B < 1 || Hk < 1 || Smax < 1)
     throw std::runtime_error("fa_decode_splits: empty shape");
-  const DeviceScope scope(device);
-  return decode_split_plan(B, Hk, Smax, device_cu_count(), num_splits)
+  const DeviceScope scope("fa_decode", device);
+  return decode_split_plan(B, Hk, Smax, device_cu_count("fa_decode"),
+                           num_splits)
       .n_splits;
 }
 
@@ -575,9 +442,9 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
     throw std::runtime_error("fa_decode: null pointer");
   if ((k_new == nullptr) != (v_new == nullptr))
     throw std::runtime_error("fa_decode: k_new and v_new go together");
-  const DeviceScope scope(device);  // `stream` is one of this device's
-  const DecodePlan plan =
-      decode_split_plan(B, Hk, Smax, device_cu_count(), n_splits);
+  const DeviceScope scope("fa_decode", device);  // `stream` is one of its
+  const DecodePlan plan = decode_split_plan(
+      B, Hk, Smax, device_cu_count("fa_decode"), n_splits);
   if (n_splits < 1 || plan.n_splits != n_splits)
     throw std::runtime_error("fa_decode: n_splits " +
                              std::to_string(n_splits) +
@@ -610,13 +477,14 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
   p.out = (__bf16*)out;
   p.lse = lse;
 
-  if (k_new != nullptr)
-    hipLaunchKernelGGL(fa_decode_append_kernel, dim3(Hk, B), dim3(32), 0,
-                       stream, (__bf16*)k_cache, (__bf16*)v_cache,
-                       (const __bf16*)k_new, (const __bf16*)v_new, seqlens,
-                       p.k_sb, p.k_sh, p.k_ss, p.v_sb, p.v_sh, p.v_ss,
-                       strides[8], strides[9], strides[10], strides[11], Smax,
-                       head_dim);
+  if (k_new != nullptr) {
+    // one new row per sequence: Sq = 1, no q_lens, row strides 0
+    const long new_strides[6] = {strides[8],  strides[9],  0,
+                                 strides[10], strides[11], 0};
+    fa_cache_append(k_cache, v_cache, k_new, v_new, seqlens, nullptr,
+                    strides + 2, new_strides, B, Hk, 1, Smax, head_dim,
+                    stream);
+  }
   const dim3 grid(n_splits, Hk, B);
   if (head_dim == 64)
     launch_decode<64>(p, grid, (long)B * H, stream);

@@ -10,7 +10,7 @@
 //   q_lens   int32 [B] or null:       n_b = clamp(q_lens[b], 0, Sq), else Sq
 //   out      [B, H, Sq, D]       any strides; lse fp32 [B, H, Sq] or null
 //
-// With new rows (k_new, v_new [B, Hk, Sq, D]) fa_extend_append_kernel first
+// With new rows (k_new, v_new [B, Hk, Sq, D]) fa_cache_append_kernel first
 // copies rows i < n_b into cache rows past_b + i (rows at or past Smax are
 // dropped) and total_b = min(past_b + n_b, Smax); without, total_b = past_b.
 // off_b = total_b - n_b. Causal: query row i < n_b sees keys 0 .. off_b + i
@@ -75,6 +75,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "attn_cache.h"
 #include "attn_decode_plan.h"
 #include "attn_frag.h"
 
@@ -82,9 +83,6 @@ namespace adapcc {
 
 namespace {
 
-constexpr float kNegBig = -3.0e38f;
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kRows = 128;          // group rows per workgroup, 32 per wave
 constexpr int kHalfImg = 4096;      // attn_frag.h's [32][64] bf16 row image
 constexpr int kImg = 2 * kHalfImg;  // 64 keys of one 64-column block
@@ -107,22 +105,6 @@ struct ExtendParams {
   __bf16* out;
   float* lse;                // [B, H, Sq], may be null
 };
-
-// The lengths of sequence b. The clamps bound every address below: a
-// malformed length cannot send a load or store outside the tensors.
-struct SeqLens {
-  int past, n, total;
-};
-
-__device__ __forceinline__ SeqLens seq_lens(const int* seqlens,
-                                            const int* q_lens, int b, int Sq,
-                                            int Smax, int append) {
-  SeqLens s;
-  s.past = min(max(seqlens[b], 0), Smax);
-  s.n = q_lens != nullptr ? min(max(q_lens[b], 0), Sq) : Sq;
-  s.total = append ? min(s.past + s.n, Smax) : s.past;
-  return s;
-}
 
 // Staging: 256 threads copy a [64 keys][kHD] tile from global to LDS. Thread
 // t moves the 16 B at column (t&7)*8 of every 64-column block of rows t>>3
@@ -157,18 +139,6 @@ __device__ __forceinline__ void st_tile(char* im, int srow, int scol,
     *reinterpret_cast<uint4*>(im + blk * kImg + kHalfImg + at) =
         t.x[2 * blk + 1];
   }
-}
-
-// Four f32 -> four bf16 (round to nearest even), one 8-byte store.
-__device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
-                                            float c, float d) {
-  unsigned lo, hi;
-  asm("v_cvt_pk_bf16_f32 %0, %2, %3\n\t"
-      "v_cvt_pk_bf16_f32 %1, %4, %5"
-      : "=&v"(lo), "=&v"(hi)
-      : "v"(a), "v"(b), "v"(c), "v"(d));
-  uint2 st = {lo, hi};
-  *reinterpret_cast<uint2*>(dst) = st;
 }
 
 // ---------------------------------------------------------------------------
@@ -290,6 +260,9 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
                    s);
         __builtin_amdgcn_s_setprio(0);
 
+        // attn_cache.h's cache_tile_step plus the s_setprio pair, written
+        // out: the call cost registers (128 / 208 VGPRs for 126 / 198) and
+        // 1.2 % at one D 128 shape (profiles/README.md, "Shared header").
         float pv[16];
         float tmax = kNegBig;
         if (kbase + 31 > wlo) {
@@ -389,9 +362,10 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// In-place cache update. Grid (ceil(Sq * D/4 / 256), Hk, B): thread e of a
-// (batch, K/V head) moves 16 B; a row is D/8 pieces of k, then D/8 of v. Rows
-// i >= n_b and rows that would land at or past Smax are left alone.
+// In-place cache update, for this file and (at Sq = 1) attn_decode.hip. Grid
+// (ceil(Sq * D/4 / 256), Hk, B): thread e of a (batch, K/V head) moves 16 B;
+// a row is D/8 pieces of k, then D/8 of v. Rows i >= n_b and rows that would
+// land at or past Smax are left alone.
 // ---------------------------------------------------------------------------
 struct AppendParams {
   __bf16 *k, *v;
@@ -402,7 +376,7 @@ struct AppendParams {
   int Sq, Smax, D;
 };
 
-__global__ __launch_bounds__(256) void fa_extend_append_kernel(
+__global__ __launch_bounds__(256) void fa_cache_append_kernel(
     AppendParams p) {
   const int hk = blockIdx.y, b = blockIdx.z;
   const SeqLens sl = seq_lens(p.seqlens, p.q_lens, b, p.Sq, p.Smax, 1);
@@ -429,19 +403,47 @@ __global__ __launch_bounds__(256) void fa_extend_append_kernel(
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Host side (bound in bindings.hip). Nothing here reads the lengths.
-//
-// strides (elements): q, k_cache, v_cache, out (b, h, row each), then k_new,
-// v_new (b, h, row each): 18 values. lse: fp32 [B, H, Sq] or null; q_lens:
-// int32 [B] or null. k_new and v_new: both or neither; with them rows
-// i < n_b are appended at seqlens[b] + i first and the attention counts
-// them. `stream` must belong to the current device.
+// Host side. Nothing here reads the lengths. fa_cache_append: attn_cache.h
+// describes the arguments.
 // ---------------------------------------------------------------------------
+void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
+                     const void* v_new, const int* seqlens, const int* q_lens,
+                     const long* cache_strides, const long* new_strides, int B,
+                     int Hk, int Sq, int Smax, int head_dim,
+                     hipStream_t stream) {
+  AppendParams a = {};
+  a.k = (__bf16*)k_cache;
+  a.v = (__bf16*)v_cache;
+  a.kn = (const __bf16*)k_new;
+  a.vn = (const __bf16*)v_new;
+  a.seqlens = seqlens;
+  a.q_lens = q_lens;
+  a.k_sb = cache_strides[0], a.k_sh = cache_strides[1];
+  a.k_ss = cache_strides[2];
+  a.v_sb = cache_strides[3], a.v_sh = cache_strides[4];
+  a.v_ss = cache_strides[5];
+  a.kn_sb = new_strides[0], a.kn_sh = new_strides[1], a.kn_ss = new_strides[2];
+  a.vn_sb = new_strides[3], a.vn_sh = new_strides[4], a.vn_ss = new_strides[5];
+  a.Sq = Sq;
+  a.Smax = Smax;
+  a.D = head_dim;
+  const long pieces = (long)Sq * (head_dim / 4);
+  hipLaunchKernelGGL(fa_cache_append_kernel,
+                     dim3((unsigned)((pieces + 255) / 256), Hk, B), dim3(256),
+                     0, stream, a);
+}
+
+// Bound in bindings.hip. strides (elements): q, k_cache, v_cache, out (b, h,
+// row each), then k_new, v_new (b, h, row each): 18 values. lse: fp32
+// [B, H, Sq] or null; q_lens: int32 [B] or null. k_new and v_new: both or
+// neither; with them rows i < n_b are appended at seqlens[b] + i first and
+// the attention counts them. device: the tensors' device index, made current
+// for the call; `stream` is one of its streams.
 void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
                int Sq, int Smax, int head_dim, const long* strides,
-               float scale, bool causal, hipStream_t stream) {
+               float scale, bool causal, int device, hipStream_t stream) {
   decode_check_shapes("fa_extend", B, H, Hk, Smax, head_dim);
   const long G = H / Hk;
   // group rows and the append's piece index stay inside int arithmetic
@@ -454,6 +456,7 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
     throw std::runtime_error("fa_extend: null pointer");
   if ((k_new == nullptr) != (v_new == nullptr))
     throw std::runtime_error("fa_extend: k_new and v_new go together");
+  const DeviceScope scope("fa_extend", device);
 
   ExtendParams p = {};
   p.q = (const __bf16*)q;
@@ -475,26 +478,10 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
   p.out = (__bf16*)out;
   p.lse = lse;
 
-  if (k_new != nullptr) {
-    AppendParams a = {};
-    a.k = (__bf16*)k_cache;
-    a.v = (__bf16*)v_cache;
-    a.kn = (const __bf16*)k_new;
-    a.vn = (const __bf16*)v_new;
-    a.seqlens = seqlens;
-    a.q_lens = q_lens;
-    a.k_sb = p.k_sb, a.k_sh = p.k_sh, a.k_ss = p.k_ss;
-    a.v_sb = p.v_sb, a.v_sh = p.v_sh, a.v_ss = p.v_ss;
-    a.kn_sb = strides[12], a.kn_sh = strides[13], a.kn_ss = strides[14];
-    a.vn_sb = strides[15], a.vn_sh = strides[16], a.vn_ss = strides[17];
-    a.Sq = Sq;
-    a.Smax = Smax;
-    a.D = head_dim;
-    const long pieces = (long)Sq * (head_dim / 4);
-    hipLaunchKernelGGL(fa_extend_append_kernel,
-                       dim3((unsigned)((pieces + 255) / 256), Hk, B),
-                       dim3(256), 0, stream, a);
-  }
+  if (k_new != nullptr)
+    fa_cache_append(k_cache, v_cache, k_new, v_new, seqlens, q_lens,
+                    strides + 3, strides + 12, B, Hk, Sq, Smax, head_dim,
+                    stream);
   const dim3 grid((unsigned)(((long)Sq * G + kRows - 1) / kRows), Hk, B);
   if (head_dim == 64)
     hipLaunchKernelGGL(fa_extend_kernel<64>, grid, dim3(256), 0, stream, p);

@@ -1,14 +1,15 @@
 """flash_attention_extend off the kernel path (fp32 on the CPU): the composed
 route against the per-sequence reference, the cache after the append, the
-argument errors, and Sq == 1 against the decode composition."""
+argument errors, and Sq == 1 against ``flash_attention_decode``."""
 
 import pytest
 import torch
 
+from attn_decode_ref import decode_reference
 from attn_extend_ref import extend_reference
 
-from adapcc_amd.ops import attention
 from adapcc_amd.ops.attention import (fa_extend_supported,
+                                      flash_attention_decode,
                                       flash_attention_extend)
 
 TOL = dict(rtol=1e-5, atol=1e-5)
@@ -76,13 +77,22 @@ def test_one_row_is_decode():
     k2, v2 = k.clone(), v.clone()
     out, lse = flash_attention_extend(q, k, v, lens_t(PAST), kn, vn,
                                       return_lse=True)
-    want, want_lse = attention._decode_composed(
-        q[:, :, 0], k2, v2, lens_t(PAST), kn[:, :, 0], vn[:, :, 0], None,
-        True)
-    torch.testing.assert_close(out[:, :, 0], want, **TOL)
-    torch.testing.assert_close(lse[:, :, 0], want_lse, **TOL)
-    # both leave a full cache (sequence 3) alone
+    k0, v0 = k2.clone(), v2.clone()
+    dec, dec_lse = flash_attention_decode(
+        q[:, :, 0], k2, v2, lens_t(PAST), kn[:, :, 0], vn[:, :, 0],
+        return_lse=True)
+    # the two public calls, bit for bit: output, lse and both caches
+    assert dec.shape == (B, H, D) and dec.is_contiguous()
+    assert torch.equal(out[:, :, 0], dec)
+    assert torch.equal(lse[:, :, 0], dec_lse)
     assert torch.equal(k, k2) and torch.equal(v, v2)
+    # both leave a full cache (sequence 3) alone
+    assert torch.equal(k[3], k0[3]) and torch.equal(v[3], v0[3])
+    # and decode is right: the reference over the appended caches
+    ref, ref_lse = decode_reference(q[:, :, 0], k2, v2,
+                                    [min(p + 1, SMAX) for p in PAST])
+    torch.testing.assert_close(dec, ref, **TOL)
+    torch.testing.assert_close(dec_lse, ref_lse, **TOL)
 
 
 def test_argument_errors():

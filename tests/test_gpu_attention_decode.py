@@ -80,11 +80,21 @@ def test_layouts_match_contiguous_bit_for_bit(num_splits):
     assert torch.equal(got, want)
 
 
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("num_splits", [1, 3])
-def test_append(num_splits):
-    B, H, Hk, D = 4, 8, 2, 128
+def test_append(num_splits, D, packed):
+    """The shared append kernel at Sq = 1. ``packed``: the new rows are
+    strided views cut from one [B, (H + 2 Hk) D] projection, as
+    ``GPT2.generate`` passes them."""
+    B, H, Hk = 4, 8, 2
     q, k, v = make(B, H, Hk, SMAX, D, seed=7)
     kn, vn = torch.randn(2, B, Hk, D, device="cuda", dtype=torch.bfloat16)
+    if packed:
+        qkv = torch.cat([t.reshape(B, -1) for t in (q, kn, vn)], dim=1)
+        q, kn, vn = (t.view(B, -1, D) for t in
+                     qkv.split([H * D, Hk * D, Hk * D], dim=1))
+        assert kn.stride(0) == (H + 2 * Hk) * D and not vn.is_contiguous()
     lens = [0, 127, 128, SMAX]                    # the last one is full
     lt = lens_t(lens)
     k0, v0 = k.clone(), v.clone()

@@ -169,6 +169,17 @@ def test_graph_replay_with_refilled_lengths():
         assert torch.equal(bits(k), bits(ke))
 
 
+def test_side_stream():
+    """The launcher makes the tensors' device current itself and launches on
+    the stream that is current for it: one call under a side stream."""
+    q, k, v, kn, vn = make(2, 8, 2, 5, 64, seed=15)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        check(q, k, v, [0, 63], kn, vn)
+    torch.cuda.current_stream().wait_stream(side)
+
+
 @pytest.mark.parametrize("H,Hk,D", [(64, 1, 64), (4, 2, 32)])
 def test_fallbacks_answer_instead_of_throwing(H, Hk, D):
     q, k, v, kn, vn = make(2, H, Hk, 9, D, seed=13)
