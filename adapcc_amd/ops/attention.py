@@ -62,9 +62,10 @@ further turn on a kept cache, drafted tokens); non-causal it is
 cross-attention over the cached keys. Its kernel (csrc/attn_extend.hip)
 gives a workgroup one K/V head and 128 rows of the flattened (position, query
 head) axis, so a K/V tile is staged once for all H // Hk heads and a short
-chunk under GQA still fills its MFMA columns. No host sync; forward only. A
-short chunk over a long cache is not split over the keys, so it leaves most
-of the chip idle.
+chunk under GQA still fills its MFMA columns. A short chunk over a long
+cache is also split over the keys, as decode is: the split count comes from
+the shapes alone, the splits leave fp32 partials and a second kernel merges
+them deterministically. No host sync; forward only.
 
 Decode is extend at Sq = 1 with new rows and no ``q_lens``, so the two share
 their host path: ``_check_cached``, ``_cached_kernel_ok``, the launch preamble
@@ -920,12 +921,23 @@ def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
 
 
 def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
-                   causal, scale, return_lse):
+                   causal, scale, return_lse, num_splits=None):
     """The kernel path, for arguments that passed ``_check_cached`` and
     ``_cached_kernel_ok``."""
+    core = _core()
     B, H, Sq, D = q.shape
     Hk, Smax = k_cache.shape[1], k_cache.shape[2]
     a = _cached_launch_args(q, k_new, v_new, return_lse)
+    ns = core.fa_extend_splits(B, Hk, Sq, H // Hk, Smax,
+                               0 if num_splits is None else int(num_splits),
+                               a.device)
+    if ns > 1:
+        o_part = torch.empty((B, H, Sq, ns, D), dtype=torch.float32,
+                             device=q.device)
+        lse_part = torch.empty((B, H, Sq, ns), dtype=torch.float32,
+                               device=q.device)
+        a.kw.update(n_splits=ns, o_part=o_part.data_ptr(),
+                    lse_part=lse_part.data_ptr())
     # [B,Sq,H,D] memory, as the forward's: transpose(1,2).view(B,Sq,C) is free
     out = torch.empty((B, Sq, H, D), dtype=q.dtype,
                       device=q.device).transpose(1, 2)
@@ -933,10 +945,10 @@ def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
         a.kw.update(q_lens=q_lens.data_ptr())
     strides = (_strides3(q) + _strides3(k_cache) + _strides3(v_cache)
                + _strides3(out) + a.new_strides)
-    _core().fa_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                      cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Sq,
-                      Smax, D, strides, scale, bool(causal), a.device,
-                      a.stream, **a.kw)
+    core.fa_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                   cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Sq,
+                   Smax, D, strides, scale, bool(causal), a.device, a.stream,
+                   **a.kw)
     return (out, a.lse) if return_lse else out
 
 
@@ -993,7 +1005,8 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
                            v_new: Optional[torch.Tensor] = None,
                            q_lens: Optional[torch.Tensor] = None,
                            causal: bool = True, scale: float = None,
-                           return_lse: bool = False):
+                           return_lse: bool = False,
+                           num_splits: Optional[int] = None):
     """Attention of a block of Sq query rows per sequence over a KV cache:
     chunked prefill, a further turn on a kept cache, a few drafted tokens,
     or (non-causal, no new rows) cross-attention. q: [B,H,Sq,D]; k_cache,
@@ -1020,15 +1033,23 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
     ``flash_attention_decode``.
 
     bf16 on the GPU with D = 64 or 128 and H // Hk <= 32 runs the CDNA4
-    kernels of csrc/attn_extend.hip; anything else is composed from a masked
-    cache rewrite and torch SDPA under the explicit mask. Forward only."""
+    kernels of csrc/attn_extend.hip; num_splits None lets the shapes decide
+    the number of key splits (one wherever Smax < 2048, and wherever the row
+    tiles alone fill the chip); an integer asks for that many, and since a
+    split is a multiple of 128 keys fewer may be used. Anything else is
+    composed from a masked cache rewrite and torch SDPA under the explicit
+    mask, which ignores num_splits. Forward only."""
     _check_cached("flash_attention_extend", q, k_cache, v_cache,
                   cache_seqlens, k_new, v_new, q_lens)
     _check_no_grad("flash_attention_extend", q, k_cache, v_cache, k_new,
                    v_new)
+    if num_splits is not None and int(num_splits) < 1:
+        raise ValueError("flash_attention_extend: num_splits must be None or "
+                         f">= 1, got {num_splits}")
     if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new,
-                              v_new, q_lens, causal, s, return_lse)
+                              v_new, q_lens, causal, s, return_lse,
+                              num_splits)
     return _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
                             q_lens, causal, scale, return_lse)

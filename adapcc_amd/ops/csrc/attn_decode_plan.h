@@ -1,7 +1,7 @@
-// Host-only part of the decode attention (attn_decode.hip): the argument
-// checks and the split policy. No device code and no HIP header, so
-// tests/cpp/decode_plan_sanitize.cpp can build it with a host compiler under
-// ASan + UBSan.
+// Host-only part of the attention over a KV cache (attn_decode.hip,
+// attn_extend.hip): the argument checks and the split policies. No device
+// code and no HIP header, so tests/cpp/decode_plan_sanitize.cpp can build it
+// with a host compiler under ASan + UBSan.
 #pragma once
 
 #include <stdexcept>
@@ -49,30 +49,63 @@ inline void decode_check_shapes(const char* name, long B, long H, long Hk,
     throw std::runtime_error(n + ": shape too large");
 }
 
-// Splits of a cache of capacity Smax. `requested` <= 0 is the policy:
-// enough splits that B * Hk * n_splits workgroups fill the chip
-// kDecodeWgPerCu times over, within the two limits above. `requested` >= 1 asks
-// for that many. Either way a split is a multiple of 128 keys, so the count
-// that comes back can be smaller than the one asked for. Shapes only: the
-// lengths never enter, so nothing has to be read back from the device and a
-// captured graph stays valid when the lengths change.
-inline DecodePlan decode_split_plan(long B, long Hk, long Smax, int n_cu,
-                                    int requested) {
-  const long max_splits = (Smax + kDecodeWgKeys - 1) / kDecodeWgKeys;
+// Splits of a cache of capacity Smax for a launch that has `groups`
+// workgroups before any split. `requested` <= 0 is the policy: enough splits
+// that groups * n_splits workgroups fill the chip wg_per_cu times over, at
+// most max_splits of them and none under min_split_keys of capacity.
+// `requested` >= 1 asks for that many. Either way a split is a multiple of
+// 128 keys, so the count that comes back can be smaller than the one asked
+// for. Shapes only: the lengths never enter, so nothing has to be read back
+// from the device and a captured graph stays valid when the lengths change.
+inline DecodePlan split_plan(long groups, long Smax, int n_cu, int requested,
+                             int wg_per_cu, int max_splits,
+                             int min_split_keys) {
+  const long most = (Smax + kDecodeWgKeys - 1) / kDecodeWgKeys;
   long n = requested;
   if (n <= 0) {
-    const long groups = B * Hk;
-    const long want = (long)kDecodeWgPerCu * (n_cu > 0 ? n_cu : 1);
+    const long want = (long)wg_per_cu * (n_cu > 0 ? n_cu : 1);
     n = (want + groups - 1) / groups;
-    if (n > kDecodeMaxSplits) n = kDecodeMaxSplits;
-    if (n > Smax / kDecodeMinSplitKeys) n = Smax / kDecodeMinSplitKeys;
+    if (n > max_splits) n = max_splits;
+    if (n > Smax / min_split_keys) n = Smax / min_split_keys;
   }
-  if (n > max_splits) n = max_splits;
+  if (n > most) n = most;
   if (n < 1) n = 1;
   long L = (Smax + n - 1) / n;
   L = (L + kDecodeWgKeys - 1) / kDecodeWgKeys * kDecodeWgKeys;
   n = (Smax + L - 1) / L;
   return {(int)n, (int)L};
+}
+
+// Decode: one workgroup per (batch, K/V head) before the split.
+inline DecodePlan decode_split_plan(long B, long Hk, long Smax, int n_cu,
+                                    int requested) {
+  return split_plan(B * Hk, Smax, n_cu, requested, kDecodeWgPerCu,
+                    kDecodeMaxSplits, kDecodeMinSplitKeys);
+}
+
+// The multi-row kernel (attn_extend.hip): its launch has row_tiles =
+// ceil(Sq * G / 128) independent workgroups per (batch, K/V head) before any
+// split, which count to the policy as batch entries do. L, a multiple of
+// 128, is a multiple of that kernel's 64-key tile. With decode's limits the
+// policy was 13 to 39 % behind the best forced count wherever few workgroups
+// meet a long cache (benchmarks/attn_bench.py --shape extend --sweep,
+// profiles/attn_extend_split.txt; the figures are in attn_extend.hip's
+// header): alone on its CU a workgroup of this kernel walks 1024 keys in 20
+// to 30 us, several times the 6 us a second launch costs, so its splits go
+// down to 256 keys and up to 32, the largest count measured. A cache under kExtendMinSmax keys is
+// not split by the policy: the calls made before the split existed (Smax
+// 1024 and under) keep their output bits, and the sweep has no shape with
+// few workgroups there, so what they would gain is not measured.
+constexpr int kExtendWgPerCu = 2;
+constexpr int kExtendMaxSplits = 32;
+constexpr int kExtendMinSplitKeys = 256;
+constexpr int kExtendMinSmax = 2048;
+
+inline DecodePlan extend_split_plan(long B, long Hk, long row_tiles,
+                                    long Smax, int n_cu, int requested) {
+  if (requested <= 0 && Smax < kExtendMinSmax) requested = 1;
+  return split_plan(B * row_tiles * Hk, Smax, n_cu, requested,
+                    kExtendWgPerCu, kExtendMaxSplits, kExtendMinSplitKeys);
 }
 
 }  // namespace adapcc

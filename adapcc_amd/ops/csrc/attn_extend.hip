@@ -58,11 +58,57 @@
 //    barrier. All lengths are clamped on the device.
 //  * Causal workgroups are issued heavy-first (blockIdx.x reversed): the
 //    last rows walk the most tiles. The effect on the tail is not measured.
+//  * A short chunk over a long cache would be a handful of workgroups, so
+//    the keys are split as in decode: extend_split_plan (attn_decode_plan.h)
+//    gives n_splits and L, a multiple of 128 keys, from the shapes alone,
+//    never from the lengths (no host sync; a captured graph stays valid when
+//    the lengths are refilled). n_splits == 1 is the launch above. Above 1
+//    the grid is (row tiles * n_splits, Hk, B), the split the minor index;
+//    the kSplit instantiation walks tiles of keys [split * L, (split + 1) * L)
+//    cut at the workgroup's largest key. L is a multiple of the 64-key tile,
+//    so the masking above, on absolute key indices, needs no new case. It
+//    stores fp32 partials from the accumulators, 16 B per lane and store:
+//    o_part[b, h, i, split, :], normalised by the split's own row sum, and
+//    lse_part[b, h, i, split]. A row with no key in the split (its limit
+//    under the split's start, padding, a dead row tile, a split past the
+//    largest key) writes lse_part = -inf and no o_part; every lse_part entry
+//    is written on every call, so the workspaces come uninitialised.
+//    fa_extend_combine_kernel, one wave per output row, skips -inf splits,
+//    weights the rest by exp(lse_s - lse_tot) in fp32, rounds once to bf16
+//    through out's strides; a row with only -inf splits gets zeros and -inf.
 //  * No atomics, no counters: deterministic.
+//
+// Split policy, measured on one MI355X (256 CUs) with benchmarks/
+// attn_bench.py --shape extend --sweep (profiles/attn_extend_split.txt: host
+// clock over back-to-back calls ended by a synchronise, candidates
+// alternating in one process, rounds within 1 % of each other but for two
+// figures under 25 us at 6 %). Sq 8, causal, us per call at forced counts of 1
+// / 2 / 4 / 8 / 16 / 32 (of which 11 and 26 are used over 4096 and 16384 keys):
+//   B1  H16 Hk4  D128 over 16384   464 / 236 / 130 / 75.9 / 52.0 / 45.2
+//   B1  H16 Hk1  D128 over 16384   492 / 245 / 126 / 74.4 / 50.8 / 44.4
+//   B1  H12 Hk1  D64  over 16384   341 / 178 / 97.5 / 57.8 / 41.8 / 38.5
+//   B1  H16 Hk4  D128 over 4096    112 / 65.2 / 40.0 / 28.5 / 24.2 / 25.0
+//   B32 H16 Hk1  D128 over 16384   525 / 292 / 165 / 102 / 84.4 / 107
+//   B32 H16 Hk4  D128 over 16384   569 / 316 / 189 / 212 / 240 / 261
+//   B32 H16 Hk16 D128 over 16384   701 / 710 / 722 / 752 / 785 / 851
+//   B8 Sq 512 H12 Hk12 D64 over 3584   119 / 111 / 121 / 150 / 231 / 512
+// Under decode's constants (at most 16 splits, none under 1024 keys) the
+// policy picked 4 splits over 4096 keys and 15 over 16384 and was 13 to 39 %
+// behind the best forced count at B1 and at B32 Hk1 (B1 Hk4 D128 over 4096:
+// 40.0 us against 24.2). Hence constants of its own: two workgroups per CU,
+// at most 32 splits (the largest count measured), none under 256 keys. With
+// them the policy is within 1.1 % of the best forced count at every shape of
+// the sweep, which is also what two timings of the same launch differ by.
+// The three shapes that lost to the composed SDPA route at one split (B1, 8
+// rows over 16384 keys) now take 45.2 us against 450 (H16 Hk4 D128), 44.5
+// against 411 (Hk1) and 38.3 against 269 (H12 Hk1 D64). Where the policy
+// gives one split the time is the parent commit's to 0.5 %.
 //
 // Resources (gfx950; profiles/attn_extend_resources.txt): head_dim 64 126
 // VGPRs, 32 KB LDS, 4 waves/SIMD by registers (three workgroups per CU
-// asked for); head_dim 128 198 VGPRs, 64 KB LDS, 2 waves/SIMD; no scratch.
+// asked for); head_dim 128 198 VGPRs, 64 KB LDS, 2 waves/SIMD; the split
+// instantiations 120 and 196 VGPRs with the same LDS; the combine kernel 18
+// and 19 VGPRs, no LDS; no scratch anywhere.
 //
 // Build: ops/build.py compiles this file with the packed fp32 VALU forms
 // off (-packed-fp32-ops), the rule for new kernel files (STATUS.md, "Known
@@ -104,6 +150,9 @@ struct ExtendParams {
   float scale;
   __bf16* out;
   float* lse;                // [B, H, Sq], may be null
+  int n_splits, L;           // key splits of a row tile, keys per split
+  float* o_part;             // [B, H, Sq, n_splits, D]   n_splits > 1
+  float* lse_part;           // [B, H, Sq, n_splits]      n_splits > 1
 };
 
 // Staging: 256 threads copy a [64 keys][kHD] tile from global to LDS. Thread
@@ -143,9 +192,11 @@ __device__ __forceinline__ void st_tile(char* im, int srow, int scol,
 
 // ---------------------------------------------------------------------------
 // Grid (ceil(Sq * G / 128), Hk, B), 256 threads = 4 waves; wave w owns group
-// rows r0 + 32 w .. + 31 of K/V head blockIdx.y.
+// rows r0 + 32 w .. + 31 of K/V head blockIdx.y. kSplit: grid.x is row tile *
+// n_splits + split, the workgroup walks keys [split * L, (split + 1) * L)
+// only and stores fp32 partials; the arithmetic of a tile is the same.
 // ---------------------------------------------------------------------------
-template <int kHD>
+template <int kHD, bool kSplit>
 __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
     ExtendParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -162,8 +213,11 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
   const int hk = blockIdx.y, b = blockIdx.z;
   const int G = p.G, H = p.H, Sq = p.Sq;
   // heavy-first: the last rows of a causal chunk walk the most tiles
-  const int bx = p.causal ? (int)(gridDim.x - 1 - blockIdx.x)
-                          : (int)blockIdx.x;
+  const int split = kSplit ? (int)(blockIdx.x % p.n_splits) : 0;
+  const int tile = kSplit ? (int)(blockIdx.x / p.n_splits) : (int)blockIdx.x;
+  const int ntiles = kSplit ? (int)(gridDim.x / p.n_splits) : (int)gridDim.x;
+  const int bx = p.causal ? ntiles - 1 - tile : tile;
+  const int k0 = kSplit ? split * p.L : 0;  // first key of this split
 
   const SeqLens sl = seq_lens(p.seqlens, p.q_lens, b, Sq, p.Smax, p.append);
   const int total = sl.total;
@@ -182,7 +236,8 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
   // largest key any row of this workgroup sees
   const int i1 = min((r0 + kRows - 1) / G, sl.n - 1);
   const int kmax = p.causal ? off + i1 : total - 1;
-  const bool live = r0 < nrows && kmax >= 0;
+  // a split that starts past it has nothing to do, like a dead row tile
+  const bool live = r0 < nrows && kmax >= k0;
 
   bool seen = false;                // does the computed row see a key
   float inv = 0.f, lse_v = -INFINITY;
@@ -194,7 +249,8 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
     const int i = r / G;
     const int h = hk * G + (r - i * G);
     const int lim = p.causal ? off + i : total - 1;  // last key this row sees
-    seen = r_own < nrows && lim >= 0;
+    // a row whose limit lies under the split sees none of its keys
+    seen = r_own < nrows && lim >= k0;
     // the wave's extremes of lim: position-major rows make it monotone
     const bool wave_on = rw < nrows;
     const int wlo = p.causal ? off + rw / G : total - 1;
@@ -220,19 +276,22 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
 
     const int srow = threadIdx.x >> 3;       // staging: this thread's row
     const int scol = (threadIdx.x & 7) * 8;  // and column (bf16)
-    const int n64 = kmax / 64 + 1;
+    // tiles t0 .. n64 - 1: L is a multiple of 64, so a split starts and
+    // (unless kmax cuts it) ends on a tile boundary
+    const int t0 = k0 / 64;
+    const int n64 = (kSplit ? min(kmax, k0 + p.L - 1) : kmax) / 64 + 1;
 
-    // prologue: stage tile 0
+    // prologue: stage the first tile
     st_tile<kHD>(kimg, srow, scol,
-                 ld_tile<kHD>(kg, p.k_ss, min(srow, klast),
-                              min(srow + 32, klast), scol));
+                 ld_tile<kHD>(kg, p.k_ss, min(k0 + srow, klast),
+                              min(k0 + srow + 32, klast), scol));
     st_tile<kHD>(vimg, srow, scol,
-                 ld_tile<kHD>(vg, p.v_ss, min(srow, klast),
-                              min(srow + 32, klast), scol));
+                 ld_tile<kHD>(vg, p.v_ss, min(k0 + srow, klast),
+                              min(k0 + srow + 32, klast), scol));
     __syncthreads();
 
     int cur = 0;
-    for (int t = 0; t < n64; ++t) {
+    for (int t = t0; t < n64; ++t) {
       // the next tile's loads fly during this one's compute
       RowTile<kHD> nk, nv;
       const bool pref = t + 1 < n64;
@@ -344,6 +403,26 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
   // epilogue: stores only. Rows past n_b and rows that saw no key get
   // explicit zeros and -inf: the output was allocated uninitialised.
   if (!own) return;
+  if constexpr (kSplit) {
+    // fp32 partial, normalised by this split's row sum, straight from the
+    // accumulators: a lane holds 4 consecutive d per (db, mq). A row without
+    // a key in this split leaves -inf and its o_part row unwritten.
+    const long at =
+        (((long)b * H + h_own) * Sq + i_own) * p.n_splits + split;
+    if (hi == 0) p.lse_part[at] = lse_v;
+    if (!seen) return;
+    float* orow = p.o_part + at * kHD;
+#pragma unroll
+    for (int db = 0; db < kNB; ++db) {
+      const f32x16& a = db == 3 ? acc3 : db == 2 ? acc2 : db ? acc1 : acc0;
+#pragma unroll
+      for (int mq = 0; mq < 4; ++mq)
+        *reinterpret_cast<float4*>(orow + db * 32 + 8 * mq + 4 * hi) =
+            make_float4(a[4 * mq] * inv, a[4 * mq + 1] * inv,
+                        a[4 * mq + 2] * inv, a[4 * mq + 3] * inv);
+    }
+    return;
+  }
   if (hi == 0 && p.lse != nullptr)
     p.lse[((long)b * H + h_own) * Sq + i_own] = lse_v;
   __bf16* orow = p.out + (long)b * p.o_sb + (long)h_own * p.o_sh +
@@ -359,6 +438,68 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
       store4_bf16(orow + db * 32 + 8 * mq + 4 * hi, o[0], o[1], o[2], o[3]);
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// Merge of the splits: one wave per output row (b, h, i), four rows per
+// workgroup: blockIdx.x * 4 + wave runs over the B * H * Sq rows in
+// lse_part's order. Lane l owns kHD/64 consecutive columns. A split with
+// lse_part = -inf is skipped and its o_part never read; a row with only
+// such splits gets zeros and lse -inf. Weights and sums in fp32, one
+// rounding to bf16, written through out's (b, h, row) strides.
+// ---------------------------------------------------------------------------
+template <int kHD>
+__global__ __launch_bounds__(256) void fa_extend_combine_kernel(
+    const float* o_part, const float* lse_part, __bf16* out, float* lse,
+    long rows, int H, int Sq, int n_splits, long o_sb, long o_sh, long o_ss) {
+  constexpr int kPer = kHD / 64;
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* lp = lse_part + row * n_splits;
+  float mx = -INFINITY;
+  for (int s = 0; s < n_splits; ++s) mx = fmaxf(mx, lp[s]);
+  float acc[kPer] = {};
+  float tot = -INFINITY;
+  if (mx > -INFINITY) {
+    float sum = 0.f;
+    for (int s = 0; s < n_splits; ++s)
+      if (lp[s] > -INFINITY) sum += expf(lp[s] - mx);
+    tot = mx + logf(sum);
+    for (int s = 0; s < n_splits; ++s) {
+      if (!(lp[s] > -INFINITY)) continue;
+      const float w = expf(lp[s] - tot);
+      const float* op = o_part + (row * n_splits + s) * kHD + lane * kPer;
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) acc[j] += w * op[j];
+    }
+  }
+  const long bh = row / Sq;
+  const long i = row - bh * Sq;
+  const long b = bh / H;
+  __bf16* dst = out + b * o_sb + (bh - b * H) * o_sh + i * o_ss + lane * kPer;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) dst[j] = (__bf16)acc[j];
+  if (lane == 0 && lse != nullptr) lse[row] = tot;
+}
+
+template <int kHD>
+void launch_extend(const ExtendParams& p, long row_tiles, int Hk, int B,
+                   hipStream_t stream) {
+  if (p.n_splits == 1) {
+    hipLaunchKernelGGL((fa_extend_kernel<kHD, false>),
+                       dim3((unsigned)row_tiles, Hk, B), dim3(256), 0, stream,
+                       p);
+    return;
+  }
+  hipLaunchKernelGGL((fa_extend_kernel<kHD, true>),
+                     dim3((unsigned)(row_tiles * p.n_splits), Hk, B),
+                     dim3(256), 0, stream, p);
+  const long rows = (long)B * p.H * p.Sq;
+  hipLaunchKernelGGL(fa_extend_combine_kernel<kHD>,
+                     dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
+                     p.o_part, p.lse_part, p.out, p.lse, rows, p.H, p.Sq,
+                     p.n_splits, p.o_sb, p.o_sh, p.o_ss);
 }
 
 // ---------------------------------------------------------------------------
@@ -433,17 +574,33 @@ void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
                      0, stream, a);
 }
 
+// The split count the policy (num_splits <= 0) or the caller (>= 1) gets for
+// these shapes (G = H / Hk) on `device`, the tensors' device index: the size
+// of the o_part / lse_part workspaces.
+int fa_extend_splits(int B, int Hk, int Sq, int G, int Smax, int num_splits,
+                     int device) {
+  if (B < 1 || Hk < 1 || Sq < 1 || G < 1 || Smax < 1)
+    throw std::runtime_error("fa_extend_splits: empty shape");
+  const DeviceScope scope("fa_extend", device);
+  return extend_split_plan(B, Hk, ((long)Sq * G + kRows - 1) / kRows, Smax,
+                           device_cu_count("fa_extend"), num_splits)
+      .n_splits;
+}
+
 // Bound in bindings.hip. strides (elements): q, k_cache, v_cache, out (b, h,
 // row each), then k_new, v_new (b, h, row each): 18 values. lse: fp32
 // [B, H, Sq] or null; q_lens: int32 [B] or null. k_new and v_new: both or
 // neither; with them rows i < n_b are appended at seqlens[b] + i first and
-// the attention counts them. device: the tensors' device index, made current
-// for the call; `stream` is one of its streams.
+// the attention counts them. n_splits: what fa_extend_splits answered; above
+// 1, o_part is fp32 [B, H, Sq, n_splits, head_dim] and lse_part fp32
+// [B, H, Sq, n_splits], neither initialised. device: the tensors' device
+// index, made current for the call; `stream` is one of its streams.
 void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
                int Sq, int Smax, int head_dim, const long* strides,
-               float scale, bool causal, int device, hipStream_t stream) {
+               float scale, bool causal, int n_splits, float* o_part,
+               float* lse_part, int device, hipStream_t stream) {
   decode_check_shapes("fa_extend", B, H, Hk, Smax, head_dim);
   const long G = H / Hk;
   // group rows and the append's piece index stay inside int arithmetic
@@ -457,6 +614,19 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
   if ((k_new == nullptr) != (v_new == nullptr))
     throw std::runtime_error("fa_extend: k_new and v_new go together");
   const DeviceScope scope("fa_extend", device);
+  const long row_tiles = ((long)Sq * G + kRows - 1) / kRows;
+  const DecodePlan plan = extend_split_plan(
+      B, Hk, row_tiles, Smax, device_cu_count("fa_extend"), n_splits);
+  if (n_splits < 1 || plan.n_splits != n_splits)
+    throw std::runtime_error("fa_extend: n_splits " +
+                             std::to_string(n_splits) +
+                             " is not a split count of this shape");
+  if (n_splits > 1 && (o_part == nullptr || lse_part == nullptr))
+    throw std::runtime_error("fa_extend: split workspaces missing");
+  // grid.x of the split launch and of the combine (four rows a workgroup)
+  if (n_splits > 1 && (row_tiles * n_splits > (1L << 30) ||
+                       (long)B * H * Sq > (1L << 32)))
+    throw std::runtime_error("fa_extend: shape too large to split");
 
   ExtendParams p = {};
   p.q = (const __bf16*)q;
@@ -477,16 +647,19 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
   p.scale = scale;
   p.out = (__bf16*)out;
   p.lse = lse;
+  p.n_splits = n_splits;
+  p.L = plan.L;
+  p.o_part = o_part;
+  p.lse_part = lse_part;
 
   if (k_new != nullptr)
     fa_cache_append(k_cache, v_cache, k_new, v_new, seqlens, q_lens,
                     strides + 3, strides + 12, B, Hk, Sq, Smax, head_dim,
                     stream);
-  const dim3 grid((unsigned)(((long)Sq * G + kRows - 1) / kRows), Hk, B);
   if (head_dim == 64)
-    hipLaunchKernelGGL(fa_extend_kernel<64>, grid, dim3(256), 0, stream, p);
+    launch_extend<64>(p, row_tiles, Hk, B, stream);
   else
-    hipLaunchKernelGGL(fa_extend_kernel<128>, grid, dim3(256), 0, stream, p);
+    launch_extend<128>(p, row_tiles, Hk, B, stream);
 }
 
 }  // namespace adapcc

@@ -132,7 +132,10 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
                int Sq, int Smax, int head_dim, const long* strides,
-               float scale, bool causal, int device, hipStream_t stream);
+               float scale, bool causal, int n_splits, float* o_part,
+               float* lse_part, int device, hipStream_t stream);
+int fa_extend_splits(int B, int Hk, int Sq, int G, int Smax, int num_splits,
+                     int device);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -449,21 +452,29 @@ PYBIND11_MODULE(_core, m) {
   // device, q_lens int32 [B] or 0, lse fp32 [B,H,Sq] or 0. strides: q,
   // k_cache, v_cache, out, k_new, v_new, (b, h, row) each. k_new, v_new != 0:
   // rows i < n_b are appended at seqlens[b] + i first. device: as for
-  // fa_decode. Nothing reads the lengths on the host.
+  // fa_decode. n_splits is what fa_extend_splits gives for the shapes (G =
+  // H / Hk; num_splits <= 0: policy); above 1, o_part fp32
+  // [B,H,Sq,n_splits,head_dim] and lse_part fp32 [B,H,Sq,n_splits] are the
+  // workspaces. Nothing reads the lengths on the host.
+  m.def("fa_extend_splits", &adapcc::fa_extend_splits, py::arg("B"),
+        py::arg("Hk"), py::arg("Sq"), py::arg("G"), py::arg("Smax"),
+        py::arg("num_splits"), py::arg("device"));
   m.def("fa_extend",
         [](uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
            uintptr_t seqlens, uintptr_t out, int B, int H, int Hk, int Sq,
            int Smax, int head_dim, const std::vector<long>& strides,
            float scale, bool causal, int device, uintptr_t stream,
            uintptr_t q_lens, uintptr_t k_new, uintptr_t v_new,
-           uintptr_t lse) {
+           uintptr_t lse, int n_splits, uintptr_t o_part,
+           uintptr_t lse_part) {
           if (strides.size() != 18)
             throw std::runtime_error("fa_extend: need 18 strides");
           adapcc::fa_extend((const void*)q, (void*)k_cache, (void*)v_cache,
                             (const int*)seqlens, (const int*)q_lens,
                             (const void*)k_new, (const void*)v_new,
                             (void*)out, (float*)lse, B, H, Hk, Sq, Smax,
-                            head_dim, strides.data(), scale, causal, device,
+                            head_dim, strides.data(), scale, causal, n_splits,
+                            (float*)o_part, (float*)lse_part, device,
                             reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
@@ -473,7 +484,9 @@ PYBIND11_MODULE(_core, m) {
         py::arg("Hk"), py::arg("Sq"), py::arg("Smax"), py::arg("head_dim"),
         py::arg("strides"), py::arg("scale"), py::arg("causal"),
         py::arg("device"), py::arg("stream"), py::arg("q_lens") = 0,
-        py::arg("k_new") = 0, py::arg("v_new") = 0, py::arg("lse") = 0);
+        py::arg("k_new") = 0, py::arg("v_new") = 0, py::arg("lse") = 0,
+        py::arg("n_splits") = 1, py::arg("o_part") = 0,
+        py::arg("lse_part") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

@@ -45,7 +45,9 @@ v_new plus the two zero-filled cache copies that prefill made, and that
 forward alone. Prints the
 time with the spread of the rounds and the achieved FLOP/s (4 * B * H * D *
 visible (row, key) pairs) or, for the short chunks, K/V bytes per second,
-and for those the workgroup count against the CUs.
+and for those the workgroup count against the CUs and the key splits the
+policy chose. --sweep adds forced split counts, the measurement behind
+keeping decode's policy constants.
 """
 import argparse
 import math
@@ -85,7 +87,7 @@ def main():
                                                        "extend"],
                     default="gpt2")
     ap.add_argument("--sweep", action="store_true",
-                    help="decode only: also time forced split counts")
+                    help="decode and extend: also time forced split counts")
     ap.add_argument("--iters", type=int, default=None,
                     help="timed calls per figure (default 20; 200 for vit, "
                          "whose calls are ~10x shorter)")
@@ -101,7 +103,7 @@ def main():
     if args.shape == "decode":
         return decode_path(args.head_dim, args.kv_heads, args.sweep)
     if args.shape == "extend":
-        return extend_path(args.head_dim, args.kv_heads)
+        return extend_path(args.head_dim, args.kv_heads, args.sweep)
     if args.shape == "varlen":
         H = 12 * 64 // args.head_dim
         if args.kv_heads:
@@ -251,8 +253,8 @@ def decode_path(D, kv_heads, sweep):
                 del q, k, v, mask, ref
 
 
-def extend_path(D, kv_heads):
-    from adapcc_amd.ops.attention import (_extend_composed,
+def extend_path(D, kv_heads, sweep):
+    from adapcc_amd.ops.attention import (_core, _extend_composed,
                                           fa_extend_supported, fa_supported,
                                           flash_attention,
                                           flash_attention_extend)
@@ -295,6 +297,12 @@ def extend_path(D, kv_heads):
                 fns["forward + 2 cache copies"] = old_prefill
                 fns["forward alone"] = lambda: flash_attention(
                     q, kn, vn, causal=True)
+            policy = _core().fa_extend_splits(B, Hk, Sq, H // Hk, Smax, 0, 0)
+            if sweep:
+                for ns in (1, 2, 4, 8, 16, 32):
+                    fns[f"extend splits={ns}"] = (
+                        lambda ns=ns: flash_attention_extend(
+                            q, k, v, lens1, num_splits=ns))
             want = _extend_composed(q.float(), k.float(), v.float(), lens1,
                                     None, None, None, True, None, False)
             err = (fns["extend"]().float() - want).abs().max().item()
@@ -305,8 +313,8 @@ def extend_path(D, kv_heads):
             wgs = B * Hk * -(-Sq * (H // Hk) // 128)
             print(f"B{B} H{H} Hk{Hk} D{D} Sq{Sq} past{past}  "
                   f"({flops / 1e9:.1f} GFLOP, K/V {nbytes / 2**20:.1f} MiB, "
-                  f"{wgs} workgroups on {n_cu} CUs, max err vs fp32 "
-                  f"{err:.2e})")
+                  f"{wgs} workgroups x {policy} splits on {n_cu} CUs, max "
+                  f"err vs fp32 {err:.2e})")
             base = None
             for name, (ms, lo, hi) in alternate(fns, window=0.3).items():
                 base = base or ms
