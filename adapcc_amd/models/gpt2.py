@@ -75,7 +75,10 @@ class CausalSelfAttention(nn.Module):
         ``flash_attention_extend`` call appends their k and v at row
         lens[b] and attends row i over lens[b] + i + 1 keys, straight off
         the projection. One token onto an existing cache with no ``q_lens``
-        is the decode step, ``flash_attention_decode``."""
+        is the decode step, ``flash_attention_decode``. With ``table``
+        (int32 [B,max_pages]) and ``page`` the cache is paged: ``k``, ``v``
+        are pools [B * max_pages, page, Hk, D] and both calls get the table
+        as ``block_table``."""
         from ..ops import attention
 
         H, Hk = self.n_head, self.n_kv_head
@@ -83,15 +86,19 @@ class CausalSelfAttention(nn.Module):
         B, T, W = qkv.shape
         D = W // (H + 2 * Hk)
         q, k, v = qkv.split([H * D, Hk * D, Hk * D], dim=-1)
+        table = cache.get("table")
         if T == 1 and "k" in cache and cache.get("q_lens") is None:
             y = attention.flash_attention_decode(
                 q.view(B, H, D), cache["k"].transpose(1, 2),
                 cache["v"].transpose(1, 2), cache["lens"],
-                k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D))
+                k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D),
+                block_table=table)
             return self.c_proj(y.view(B, 1, H * D))
         if "k" not in cache:
-            cache["k"] = qkv.new_empty(B, cache["Smax"], Hk, D)
-            cache["v"] = qkv.new_empty(B, cache["Smax"], Hk, D)
+            shape = ((B, cache["Smax"]) if table is None
+                     else (table.numel(), cache["page"]))
+            cache["k"] = qkv.new_empty(*shape, Hk, D)
+            cache["v"] = qkv.new_empty(*shape, Hk, D)
         lens = cache.get("lens")
         if lens is None:
             lens = torch.zeros(B, dtype=torch.int32, device=x.device)
@@ -100,7 +107,7 @@ class CausalSelfAttention(nn.Module):
             cache["v"].transpose(1, 2), lens,
             k_new=k.view(B, T, Hk, D).transpose(1, 2),
             v_new=v.view(B, T, Hk, D).transpose(1, 2),
-            q_lens=cache.get("q_lens"))
+            q_lens=cache.get("q_lens"), block_table=table)
         return self.c_proj(y.transpose(1, 2).view(B, T, H * D))
 
     def forward(self, x: torch.Tensor,
@@ -278,7 +285,8 @@ class GPT2(nn.Module):
     def generate(self, idx: torch.Tensor, max_new_tokens: int,
                  return_logits: bool = False,
                  prompt_lens: torch.Tensor = None,
-                 prefill_chunk: int = None):
+                 prefill_chunk: int = None,
+                 kv_page_size: int = None):
         """Greedy continuation of the prompts idx [B,T], T + max_new_tokens
         <= n_positions: returns [B, T + max_new_tokens], and with
         ``return_logits`` also the [B, max_new_tokens, vocab] logits each
@@ -299,7 +307,15 @@ class GPT2(nn.Module):
         attends in one pass at any length; every further token is one pass
         over [B,1,C] through ``flash_attention_decode``. Lengths and
         position ids stay on the device: neither the prefill nor the loop
-        has a host sync. No dropout, whatever the module's mode."""
+        has a host sync. No dropout, whatever the module's mode.
+
+        ``kv_page_size`` P pages the caches: each layer holds pools
+        [B * max_pages, P, Hk, D], max_pages = ceil((T + max_new_tokens) /
+        P), and all layers share one int32 block table [B, max_pages] that
+        hands the pages out interleaved across the sequences (page j of
+        sequence b is pool page j * B + b), which every prefill chunk and
+        decode step passes as ``block_table``. The tokens are the unpaged
+        run's."""
         B, T = idx.shape
         total = T + max_new_tokens
         if T < 1 or max_new_tokens < 1 or total > self.cfg.n_positions:
@@ -320,7 +336,18 @@ class GPT2(nn.Module):
             plens = prompt_lens.clamp(1, T)
         else:
             plens = torch.full((B,), T, dtype=torch.int32, device=idx.device)
+        batch = torch.arange(B, device=idx.device)
         caches = [{"Smax": total} for _ in self.h]
+        if kv_page_size is not None:
+            P = int(kv_page_size)
+            if P < 1:
+                raise ValueError("GPT2.generate: kv_page_size must be >= 1, "
+                                 f"got {kv_page_size}")
+            max_pages = -(-total // P)
+            table = (torch.arange(max_pages, device=idx.device).view(1, -1)
+                     * B + batch.view(B, 1)).to(torch.int32)
+            for cache in caches:
+                cache.update(page=P, table=table)
 
         def hidden(x):
             for block, cache in zip(self.h, caches):
@@ -331,7 +358,6 @@ class GPT2(nn.Module):
             return self.lm_head(self.ln_f(x.unsqueeze(1)))[:, 0]
 
         # prefill: last[b] is the hidden state at position plens[b] - 1
-        batch = torch.arange(B, device=idx.device)
         last = None
         for c0 in range(0, T, chunk):
             n = min(chunk, T - c0)

@@ -72,6 +72,17 @@ their host path: ``_check_cached``, ``_cached_kernel_ok``, the launch preamble
 ``_cached_launch_args``, one append kernel (csrc/attn_cache.h) and, off the
 kernel path, ``_extend_composed`` (a masked rewrite of the caches, then torch
 SDPA under the explicit mask), which decode calls on ``unsqueeze(2)`` views.
+
+Both calls also take a paged cache: with ``block_table`` (int32
+[B,max_pages] on the device) k_cache and v_cache are pools [N,Hk,P,D] of N
+pages of P key rows, logical row j of sequence b lives in row j % P of page
+block_table[b, j // P], and max_pages * P stands where Smax did. The kernels
+look the page up themselves (csrc/attn_cache.h's ``paged_offset``; entries
+clamped to [0, N-1] on the device), so nothing is gathered, the table is
+never read on the host, and memory grows with the tokens held, sequences of
+any lengths share one pool and a common prefix is stored once. P must be a
+power of two >= 16 there; ``_paged_composed`` (gather, compose, write the
+appended rows back) is the route for everything else and the definition.
 """
 
 from __future__ import annotations
@@ -703,21 +714,43 @@ def flash_attention_qkv_varlen(qkv: torch.Tensor, n_head: int,
 # extend (a block of rows) share
 # ---------------------------------------------------------------------------
 _DECODE_MAX_GROUP = 32  # csrc/attn_decode_plan.h's kDecodeMaxGroup
+_PAGED_MAX_KEYS = 1 << 30   # its bound on Smax, for max_pages * P
 
 
 def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                  q_lens=None) -> None:
+                  q_lens=None, block_table=None) -> None:
     """The argument checks of the calls over a KV cache. q is [B,H,D]
     (decode) or [B,H,Sq,D] (extend), new rows then [B,Hk,D] or [B,Hk,Sq,D];
-    q_lens (extend) like cache_seqlens."""
+    q_lens (extend) like cache_seqlens. With block_table (int32
+    [B,max_pages]) the caches are page pools [N,Hk,P,D]."""
     rows = "" if name.endswith("decode") else "Sq,"
+    paged = block_table is not None
+    form = "[N,Hk,P,D]" if paged else "[B,Hk,Smax,D]"
     if (q.dim() != (4 if rows else 3) or k_cache.dim() != 4
             or k_cache.shape != v_cache.shape):
         raise ValueError(f"{name}: need q [B,H,{rows}D] and k_cache, v_cache "
-                         f"[B,Hk,Smax,D] of one shape, got {tuple(q.shape)}, "
+                         f"{form} of one shape, got {tuple(q.shape)}, "
                          f"{tuple(k_cache.shape)}, {tuple(v_cache.shape)}")
     B, H, D = q.shape[0], q.shape[1], q.shape[-1]
     Bk, Hk, Smax, Dk = k_cache.shape
+    if paged:
+        if not isinstance(block_table, torch.Tensor):
+            raise ValueError(f"{name}: block_table must be a tensor")
+        if block_table.dtype != torch.int32:
+            raise ValueError(f"{name}: block_table must be int32, got "
+                             f"{block_table.dtype}")
+        if (block_table.dim() != 2 or block_table.shape[0] != B
+                or block_table.shape[1] < 1):
+            raise ValueError(f"{name}: block_table must be [B,max_pages] = "
+                             f"[{B},>=1], got {tuple(block_table.shape)}")
+        if block_table.device != q.device:
+            raise ValueError(f"{name}: block_table is on "
+                             f"{block_table.device}, the inputs on {q.device}")
+        if block_table.shape[1] * Smax > _PAGED_MAX_KEYS:
+            raise ValueError(f"{name}: max_pages * P = "
+                             f"{block_table.shape[1]} * {Smax} keys is over "
+                             f"2^30")
+        Bk = B      # the pool's first dimension counts pages, not sequences
     if Bk != B or Dk != D or min(*q.shape, Hk, Smax) < 1:
         raise ValueError(f"{name}: q {tuple(q.shape)} and the caches "
                          f"{tuple(k_cache.shape)} do not agree in batch and "
@@ -763,9 +796,14 @@ def _check_no_grad(name, *tensors) -> None:
 
 
 def _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens,
-                      q_lens=None) -> bool:
+                      q_lens=None, block_table=None) -> bool:
     """Where the cached calls run their kernels, for arguments that
     ``_check_cached`` has passed."""
+    if block_table is not None:
+        P = k_cache.shape[2]
+        # the kernels split a row index with a shift and a mask
+        if P < 16 or P & (P - 1) or not block_table.is_contiguous():
+            return False
     if not (q.is_cuda and q.dtype == torch.bfloat16):
         return False
     if q.shape[-1] not in (64, 128):
@@ -788,13 +826,21 @@ class _CachedLaunch(NamedTuple):
     lse: Optional[torch.Tensor]     # fp32, q's shape without D, or None
     device: int         # q's index: the launchers make it current
     stream: int         # that device's current stream
+    Smax: int           # the cache's capacity: max_pages * P when paged
     # the tensors kw's k_new, v_new point into (contiguous copies of rows not
     # 16-B aligned): alive while the launcher holds this result
     new_rows: Optional[tuple]
 
 
-def _cached_launch_args(q, k_new, v_new, return_lse) -> _CachedLaunch:
+def _cached_launch_args(q, k_cache, k_new, v_new, return_lse,
+                        block_table=None) -> _CachedLaunch:
     kw = {}
+    Smax = k_cache.shape[2]
+    if block_table is not None:
+        N, P, max_pages = k_cache.shape[0], Smax, block_table.shape[1]
+        kw.update(block_table=block_table.data_ptr(), n_pages=N, page_size=P,
+                  max_pages=max_pages)
+        Smax = max_pages * P
     new_rows = None
     new_strides = [0] * (2 * (q.dim() - 1))
     if k_new is not None:
@@ -809,7 +855,7 @@ def _cached_launch_args(q, k_new, v_new, return_lse) -> _CachedLaunch:
         kw.update(lse=lse.data_ptr())
     return _CachedLaunch(kw, new_strides, lse, q.get_device(),
                          torch.cuda.current_stream(q.device).cuda_stream,
-                         new_rows)
+                         Smax, new_rows)
 
 
 # ---------------------------------------------------------------------------
@@ -817,26 +863,30 @@ def _cached_launch_args(q, k_new, v_new, return_lse) -> _CachedLaunch:
 # ---------------------------------------------------------------------------
 def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor,
-                        cache_seqlens: torch.Tensor) -> bool:
+                        cache_seqlens: torch.Tensor,
+                        block_table: Optional[torch.Tensor] = None) -> bool:
     """True where ``flash_attention_decode`` runs its kernels: bf16 on the
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
-    contiguous and 16-B aligned, extension built."""
+    contiguous and 16-B aligned, extension built; with ``block_table`` also
+    a page size that is a power of two >= 16 and a contiguous table."""
     try:
         _check_cached("flash_attention_decode", q, k_cache, v_cache,
-                      cache_seqlens, None, None)
+                      cache_seqlens, None, None, None, block_table)
     except ValueError:
         return False
-    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens)
+    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, None,
+                             block_table)
 
 
 def _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
-                   num_splits, return_lse):
+                   num_splits, return_lse, block_table=None):
     """The kernel path, for arguments that passed ``_check_cached`` and
     ``_cached_kernel_ok``."""
     core = _core()
     B, H, D = q.shape
-    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
-    a = _cached_launch_args(q, k_new, v_new, return_lse)
+    Hk = k_cache.shape[1]
+    a = _cached_launch_args(q, k_cache, k_new, v_new, return_lse, block_table)
+    Smax = a.Smax
     ns = core.fa_decode_splits(B, Hk, Smax,
                                0 if num_splits is None else int(num_splits),
                                a.device)
@@ -862,7 +912,8 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                            v_new: Optional[torch.Tensor] = None,
                            scale: float = None,
                            num_splits: Optional[int] = None,
-                           return_lse: bool = False):
+                           return_lse: bool = False,
+                           block_table: Optional[torch.Tensor] = None):
     """Attention of one new token per sequence over a KV cache. q: [B,H,D];
     k_cache, v_cache: [B,Hk,Smax,D] with H % Hk == 0 and any batch, head and
     row strides (a [B,Smax,Hk,D] cache goes in as its transposed view), query
@@ -884,22 +935,27 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
     split-KV kernels; num_splits None lets the shapes decide the number of
     key splits, an integer asks for that many (the kernels only). Anything
     else is composed as ``flash_attention_extend`` composes a block of one
-    row. Forward only."""
+    row. Forward only.
+
+    With ``block_table`` (int32 [B,max_pages]) the cache is paged: k_cache
+    and v_cache are pools [N,Hk,P,D] and Smax = max_pages * P, as
+    ``flash_attention_extend`` describes."""
     _check_cached("flash_attention_decode", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new)
+                  cache_seqlens, k_new, v_new, None, block_table)
     _check_no_grad("flash_attention_decode", q, k_cache, v_cache, k_new,
                    v_new)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("flash_attention_decode: num_splits must be None or "
                          f">= 1, got {num_splits}")
-    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens):
+    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, None,
+                         block_table):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new,
-                              v_new, s, num_splits, return_lse)
+                              v_new, s, num_splits, return_lse, block_table)
     # a block of one row; [B,1,H,D] memory, so the [B,H,D] result is contiguous
     one = [None if t is None else t.unsqueeze(2) for t in (q, k_new, v_new)]
     res = _extend_composed(one[0], k_cache, v_cache, cache_seqlens, one[1],
-                           one[2], None, True, scale, return_lse)
+                           one[2], None, True, scale, return_lse, block_table)
     return (res[0][:, :, 0], res[1][:, :, 0]) if return_lse else res[:, :, 0]
 
 
@@ -908,26 +964,31 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
 # ---------------------------------------------------------------------------
 def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
-                        q_lens: Optional[torch.Tensor] = None) -> bool:
+                        q_lens: Optional[torch.Tensor] = None,
+                        block_table: Optional[torch.Tensor] = None) -> bool:
     """True where ``flash_attention_extend`` runs its kernels: bf16 on the
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
-    contiguous and 16-B aligned, extension built."""
+    contiguous and 16-B aligned, extension built; with ``block_table`` also
+    a page size that is a power of two >= 16 and a contiguous table."""
     try:
         _check_cached("flash_attention_extend", q, k_cache, v_cache,
-                      cache_seqlens, None, None, q_lens)
+                      cache_seqlens, None, None, q_lens, block_table)
     except ValueError:
         return False
-    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens)
+    return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens,
+                             block_table)
 
 
 def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
-                   causal, scale, return_lse, num_splits=None):
+                   causal, scale, return_lse, num_splits=None,
+                   block_table=None):
     """The kernel path, for arguments that passed ``_check_cached`` and
     ``_cached_kernel_ok``."""
     core = _core()
     B, H, Sq, D = q.shape
-    Hk, Smax = k_cache.shape[1], k_cache.shape[2]
-    a = _cached_launch_args(q, k_new, v_new, return_lse)
+    Hk = k_cache.shape[1]
+    a = _cached_launch_args(q, k_cache, k_new, v_new, return_lse, block_table)
+    Smax = a.Smax
     ns = core.fa_extend_splits(B, Hk, Sq, H // Hk, Smax,
                                0 if num_splits is None else int(num_splits),
                                a.device)
@@ -952,11 +1013,60 @@ def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
     return (out, a.lse) if return_lse else out
 
 
+def _paged_composed(q, k_pool, v_pool, block_table, cache_seqlens, k_new,
+                    v_new, q_lens, causal, scale, return_lse):
+    """The paged calls off the kernel path, and their definition: the
+    table's pages gathered into [B,Hk,Smax,D] slabs (entries clamped to
+    [0, N-1], as the kernels clamp them), ``_extend_composed`` on the slabs,
+    then the appended rows alone written back into the pools; no host sync.
+    The write-back is a masked rewrite through an inverse index: pool row
+    (page, r) takes new row inv[page * P + r] where that is >= 0. A dropped
+    row scatters its index into one dummy slot past the pool, so there is
+    neither a ``nonzero`` nor a duplicate target among the real slots."""
+    B, Sq = q.shape[0], q.shape[2]
+    N, Hk, P, D = k_pool.shape
+    max_pages = block_table.shape[1]
+    Smax = max_pages * P
+    table = block_table.clamp(0, N - 1).long()            # [B,max_pages]
+
+    def slab(pool):     # [B,max_pages,Hk,P,D] -> [B,Hk,Smax,D]
+        return pool[table].transpose(1, 2).reshape(B, Hk, Smax, D)
+
+    k_slab, v_slab = slab(k_pool), slab(v_pool)
+    res = _extend_composed(q, k_slab, v_slab, cache_seqlens, k_new, v_new,
+                           q_lens, causal, scale, return_lse)
+    if k_new is None:
+        return res
+    past = cache_seqlens.clamp(0, Smax).view(B, 1).long()
+    n = (torch.full_like(cache_seqlens, Sq) if q_lens is None
+         else q_lens.clamp(0, Sq)).view(B, 1)
+    i = torch.arange(Sq, device=q.device).view(1, Sq)
+    row = past + i                                        # [B,Sq]
+    kept = (i < n) & (row < Smax)
+    row = row.clamp(max=Smax - 1)
+    slot = table.gather(1, row // P) * P + row % P
+    slot = torch.where(kept, slot, N * P)
+    inv = torch.full((N * P + 1,), -1, dtype=torch.long, device=q.device)
+    inv.scatter_(0, slot.reshape(-1), torch.arange(B * Sq, device=q.device))
+    inv = inv[:N * P].view(N, P)
+    hit = (inv >= 0).view(N, 1, P, 1)
+    for pool, new in ((k_pool, k_new), (v_pool, v_new)):
+        src = new.transpose(1, 2).reshape(B * Sq, Hk, D)
+        pool.copy_(torch.where(hit, src[inv.clamp(min=0)].transpose(1, 2),
+                               pool))
+    return res
+
+
 def _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
-                     causal, scale, return_lse):
+                     causal, scale, return_lse, block_table=None):
     """The append as one gathered, masked rewrite of the caches in place (an
     index_put without duplicate targets), then SDPA under the explicit
-    [B,1,Sq,Smax] mask; no host sync."""
+    [B,1,Sq,Smax] mask; no host sync. With a block_table: ``_paged_composed``
+    around this."""
+    if block_table is not None:
+        return _paged_composed(q, k_cache, v_cache, block_table,
+                               cache_seqlens, k_new, v_new, q_lens, causal,
+                               scale, return_lse)
     B, H, Sq, D = q.shape
     Hk, Smax = k_cache.shape[1], k_cache.shape[2]
     dev = q.device
@@ -1006,7 +1116,8 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
                            q_lens: Optional[torch.Tensor] = None,
                            causal: bool = True, scale: float = None,
                            return_lse: bool = False,
-                           num_splits: Optional[int] = None):
+                           num_splits: Optional[int] = None,
+                           block_table: Optional[torch.Tensor] = None):
     """Attention of a block of Sq query rows per sequence over a KV cache:
     chunked prefill, a further turn on a kept cache, a few drafted tokens,
     or (non-causal, no new rows) cross-attention. q: [B,H,Sq,D]; k_cache,
@@ -1038,18 +1149,39 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
     tiles alone fill the chip); an integer asks for that many, and since a
     split is a multiple of 128 keys fewer may be used. Anything else is
     composed from a masked cache rewrite and torch SDPA under the explicit
-    mask, which ignores num_splits. Forward only."""
+    mask, which ignores num_splits. Forward only.
+
+    With ``block_table`` the cache is paged. k_cache and v_cache are then
+    page pools [N,Hk,P,D], N pages of P key rows, with any page, head and
+    row strides (a [N,P,Hk,D] pool goes in as its transposed view), and
+    block_table is int32 [B,max_pages] on the same device: logical key row
+    j of sequence b is row j % P of page block_table[b, j // P]. Smax =
+    max_pages * P takes the slab's capacity everywhere above: the clamps of
+    cache_seqlens, the drop of appended rows, the split plan. New rows are
+    written in place at logical rows past_b + i, through the table. The
+    table promises, unchecked: entries 0 .. ceil(total_b / P) - 1 of row b
+    name the sequence's pages; later entries may hold anything and are not
+    read; two rows may name one page (a shared prefix) as long as no call
+    appends into it. Every entry that is read is clamped to [0, N-1] first,
+    so a malformed table gives unspecified values but no access outside the
+    pools. The table is never read on the host: a captured graph stays
+    valid when lengths and entries are refilled. The kernels take P a power
+    of two >= 16 and a contiguous table, and give the output bits of the
+    unpaged call on the gathered slab of the same Smax and split count;
+    anything else gathers the pages, composes as above and writes the
+    appended rows back."""
     _check_cached("flash_attention_extend", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new, q_lens)
+                  cache_seqlens, k_new, v_new, q_lens, block_table)
     _check_no_grad("flash_attention_extend", q, k_cache, v_cache, k_new,
                    v_new)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("flash_attention_extend: num_splits must be None or "
                          f">= 1, got {num_splits}")
-    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens):
+    if _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens,
+                         block_table):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new,
                               v_new, q_lens, causal, s, return_lse,
-                              num_splits)
+                              num_splits, block_table)
     return _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                            q_lens, causal, scale, return_lse)
+                            q_lens, causal, scale, return_lse, block_table)

@@ -1,7 +1,9 @@
 // What the two attention kernels over a KV cache share (gfx950, bf16):
 // attn_decode.hip (one query row per sequence, split over the keys) and
 // attn_extend.hip (a block of rows): the clamped lengths of a sequence, the
-// cache append's interface (one kernel, in attn_extend.hip), the host
+// map from a logical key row to its place in a paged cache (PageMap,
+// paged_offset: every K, V and append address of the kPaged instantiations),
+// the cache append's interface (one kernel, in attn_extend.hip), the host
 // helpers that make the tensors' device current, and cache_tile_step, the
 // span from the finished score tile to the last PV MFMA. Decode calls it;
 // extend holds the same span written out (with an s_setprio pair), since as
@@ -15,6 +17,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "attn_decode_plan.h"
 #include "attn_frag.h"
 
 namespace adapcc {
@@ -40,6 +43,48 @@ __device__ __forceinline__ SeqLens seq_lens(const int* seqlens,
   s.n = q_lens != nullptr ? min(max(q_lens[b], 0), Sq) : Sq;
   s.total = append ? min(s.past + s.n, Smax) : s.past;
   return s;
+}
+
+// A paged cache (the kPaged instantiations): k and v are pools [N, Hk, P, D]
+// of N pages of P = 1 << lg key rows, and logical key row j of sequence b is
+// row j & (P - 1) of page table[b * max_pages + (j >> lg)]. The pool's
+// (page, head, row) strides travel where a slab's (batch, head, row) strides
+// do, and Smax = max_pages * P. table == nullptr: not paged.
+struct PageMap {
+  const int* table;  // int32 [B, max_pages], rows contiguous
+  int max_pages, n_pages, lg;
+};
+
+// The one place a table entry becomes an address. page_base: the element
+// offset of the page that holds logical row `row` of the sequence whose
+// table row is `trow`; the entry is clamped to [0, N - 1] first, so a
+// malformed table gives unspecified values but no access outside the pool
+// (what seq_lens does for lengths). The caller has clamped `row` to
+// [0, total_b - 1], so row >> lg < max_pages and no entry past the
+// sequence's pages is read. With a wave-uniform `row` the load is scalar.
+__device__ __forceinline__ long page_base(const PageMap& pm, const int* trow,
+                                          int row, long page_stride) {
+  const int page = min(max(trow[row >> pm.lg], 0), pm.n_pages - 1);
+  return (long)page * page_stride;
+}
+
+// Logical row -> element offset inside one head's plane of the pool.
+__device__ __forceinline__ long paged_offset(const PageMap& pm,
+                                             const int* trow, int row,
+                                             long page_stride,
+                                             long row_stride) {
+  return page_base(pm, trow, row, page_stride) +
+         (long)(row & ((1 << pm.lg) - 1)) * row_stride;
+}
+
+// The same for a row known to lie in the page of `urow` (a tile that does
+// not straddle a page: one lookup, by the wave-uniform urow, for all lanes).
+__device__ __forceinline__ long paged_offset_in(const PageMap& pm,
+                                                const int* trow, int urow,
+                                                int row, long page_stride,
+                                                long row_stride) {
+  return page_base(pm, trow, urow, page_stride) +
+         (long)(row & ((1 << pm.lg) - 1)) * row_stride;
 }
 
 // Four f32 -> four bf16 (round to nearest even), one 8-byte store.
@@ -134,12 +179,33 @@ __device__ __forceinline__ void cache_tile_step(
 // to cache rows past_b + i; rows that would land at or past Smax are dropped,
 // so a full cache is left alone. cache_strides: k_cache, then v_cache, (b, h,
 // row) each; new_strides: k_new, then v_new, likewise. q_lens may be null.
-// The caller has checked the shapes and made the device current.
+// The caller has checked the shapes and made the device current. With
+// pages.table the caches are pools, cache_strides their (page, head, row)
+// strides and Smax = max_pages * P: cache row past_b + i is found through
+// paged_offset.
 void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
                      const void* v_new, const int* seqlens, const int* q_lens,
                      const long* cache_strides, const long* new_strides, int B,
                      int Hk, int Sq, int Smax, int head_dim,
-                     hipStream_t stream);
+                     const PageMap& pages, hipStream_t stream);
+
+// The PageMap of a host call, checked (attn_decode_plan.h): block_table null
+// is the unpaged call and gives table == nullptr; else Smax must be
+// max_pages * page_size.
+inline PageMap make_page_map(const char* name, const int* block_table,
+                             int n_pages, int page_size, int max_pages,
+                             int Smax) {
+  PageMap pm = {};
+  if (block_table == nullptr) return pm;
+  pm.lg = paged_check_shapes(name, n_pages, page_size, max_pages);
+  if ((long)max_pages * page_size != Smax)
+    throw std::runtime_error(std::string(name) +
+                             ": Smax must be max_pages * page_size");
+  pm.table = block_table;
+  pm.max_pages = max_pages;
+  pm.n_pages = n_pages;
+  return pm;
+}
 
 // Makes `device` HIP's current device for the scope of a host call, so the
 // launches (and decode's CU count) belong to the device the tensors and the

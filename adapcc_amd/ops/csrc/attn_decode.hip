@@ -49,6 +49,22 @@
 //    cache is left alone.
 //  * From the score tile to the last PV MFMA a sub-tile runs attn_cache.h's
 //    cache_tile_step (attn_extend.hip holds the same span written out).
+//  * Paged cache (block_table != null; fa_decode_kernel<., true>): the
+//    caches are pools [N, Hk, P, D] under an int32 [B, max_pages] table
+//    (attn_extend.hip's header has the layout), Smax = max_pages * P. Only
+//    the loads differ: a lane's K row (ld_kfrag) and the four rows of its V
+//    share (ld_sub) go through attn_cache.h's paged_offset after their clamp
+//    to the split's last key. A 32-key sub-tile lies in one page for P >= 32
+//    (one scalar lookup a sub-tile) and in two for P = 16 (a lookup per
+//    row). No barrier is added; split plan, partials and combine are
+//    untouched, so the output bits are the unpaged call's on the gathered
+//    slab. Measured (profiles/attn_paged.txt; contiguous / paged at P 16,
+//    64, 256, us, two timings of one code within 0.3 %), 16384 keys: B32 H16
+//    Hk4 D128 180 / 185, 182, 183 (5.95 / 5.80, 5.89, 5.86 TB/s); B1 H16
+//    Hk16 D128 30.2 / 32.0, 31.9, 32.1. By reasoning, not by a trace: the
+//    2 to 5 us are the dependent table load ahead of each sub-tile's loads,
+//    first of all the first one's, which nothing overlaps; the entry is not
+//    fetched a sub-tile ahead (not tried). Gathering the pages first costs 1075 and 169 us.
 //
 // How a wave gets its K fragment (32 keys x 16 columns, 16 B of one key row
 // per lane): each lane loads its 16 B straight from global in fragment
@@ -90,7 +106,8 @@
 //
 // Resources (gfx950; profiles/attn_decode_resources.txt): head_dim 64 159
 // VGPRs, 33 KB LDS, 3 waves/SIMD; head_dim 128 242 VGPRs, 65 KB LDS, 2
-// waves/SIMD; no scratch. LDS is sized by the merge (a wave's O^T, 32 x kHD
+// waves/SIMD; paged 148 and 240 VGPRs, the same LDS and occupancy; no
+// scratch. LDS is sized by the merge (a wave's O^T, 32 x kHD
 // fp32), which K direct does not shrink.
 //
 // Build: ops/build.py compiles this file with the packed fp32 VALU forms
@@ -133,7 +150,22 @@ struct DecodeParams {
   float* lse_part;          // [B, H, n_splits]      n_splits > 1
   __bf16* out;              // [B, H, D] contiguous
   float* lse;               // [B, H], may be null
+  PageMap pg;               // kPaged: k, v are pools, k_sb, v_sb page strides
 };
+
+// kPaged: where a wave's loads find key row `row` (clamped to the split's
+// last key, so inside the sub-tile that starts at kb) of a page pool. kb is
+// a multiple of 32: with 32 rows or more to a page the sub-tile lies in one
+// page and one wave-uniform (scalar) lookup serves every lane; at 16 it
+// lies in two and each lane looks up its own row.
+__device__ __forceinline__ long paged_sub_offset(const PageMap& pm,
+                                                 const int* trow, int kb,
+                                                 int row, long sp, long ss) {
+  if (pm.lg >= 5)
+    return paged_offset_in(pm, trow, __builtin_amdgcn_readfirstlane(kb), row,
+                           sp, ss);
+  return paged_offset(pm, trow, row, sp, ss);
+}
 
 // One wave's share of a [32 keys][kHD] sub-tile: per 64-column block, lane t
 // moves the 16 B at column (t&7)*8 of rows (t>>3) + 8*i, i = 0..3, so every
@@ -156,6 +188,25 @@ __device__ __forceinline__ SubTile<kHD> ld_sub(const __bf16* g, long ss,
     t.x[j] = *reinterpret_cast<const u32x4*>(g + (long)row * ss +
                                              (j >> 2) * 64 + col);
   }
+  return t;
+}
+
+// kPaged: the same share, its four rows found through the block table.
+template <int kHD>
+__device__ __forceinline__ SubTile<kHD> ld_sub_paged(
+    const __bf16* g, const PageMap& pm, const int* trow, long sp, long ss,
+    int kb, int klast, int lane) {
+  SubTile<kHD> t;
+  const int col = (lane & 7) * 8;
+  long off[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    off[i] = paged_sub_offset(pm, trow, kb,
+                              min(kb + (lane >> 3) + 8 * i, klast), sp, ss);
+#pragma unroll
+  for (int j = 0; j < kHD / 16; ++j)
+    t.x[j] = *reinterpret_cast<const u32x4*>(g + off[j & 3] + (j >> 2) * 64 +
+                                             col);
   return t;
 }
 
@@ -189,6 +240,21 @@ __device__ __forceinline__ KFrag<kHD> ld_kfrag(const __bf16* g, long ss,
   return t;
 }
 
+// kPaged: the lane's key row found through the block table.
+template <int kHD>
+__device__ __forceinline__ KFrag<kHD> ld_kfrag_paged(
+    const __bf16* g, const PageMap& pm, const int* trow, long sp, long ss,
+    int kb, int klast, int lane) {
+  KFrag<kHD> t;
+  const int row = min(kb + (lane & 31), klast);
+  const __bf16* r =
+      g + paged_sub_offset(pm, trow, kb, row, sp, ss) + (lane >> 5) * 8;
+#pragma unroll
+  for (int c = 0; c < kHD / 16; ++c)
+    t.f[c] = *reinterpret_cast<const bf16x8*>(r + c * 16);
+  return t;
+}
+
 // Orders this wave's LDS writes and reads for the compiler; the hardware
 // serves one wave's LDS instructions in order.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -198,9 +264,11 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 // ---------------------------------------------------------------------------
 // Partial attention of one (batch, K/V head, key split).
-// Grid (n_splits, Hk, B), 256 threads = 4 waves.
+// Grid (n_splits, Hk, B), 256 threads = 4 waves. kPaged: K and V rows come
+// from a page pool through the block table; only the loads differ, and the
+// main loop still has no workgroup barrier.
 // ---------------------------------------------------------------------------
-template <int kHD>
+template <int kHD, bool kPaged>
 __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
     DecodeParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -253,8 +321,11 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
   for (int c = 0; c < kNC; ++c)
     qf[c] = *reinterpret_cast<const bf16x8*>(qrow + c * 16 + hi * 8);
 
-  const __bf16* kg = p.k + (long)b * p.k_sb + (long)hk * p.k_sh;
-  const __bf16* vg = p.v + (long)b * p.v_sb + (long)hk * p.v_sh;
+  // paged: the head's plane of the pool; the page comes per sub-tile or row
+  const __bf16* kg = p.k + (kPaged ? 0 : (long)b * p.k_sb) + (long)hk * p.k_sh;
+  const __bf16* vg = p.v + (kPaged ? 0 : (long)b * p.v_sb) + (long)hk * p.v_sh;
+  [[maybe_unused]] const int* trow =
+      kPaged ? p.pg.table + (long)b * p.pg.max_pages : nullptr;
   char* const vim = smem + wave * kWaveBytes;
 
   // O^T, one accumulator per 32 columns; acc2, acc3 (columns 64..127) are
@@ -270,8 +341,14 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
   SubTile<kHD> nv;
   KFrag<kHD> nk;
   if (kb < kend) {
-    nk = ld_kfrag<kHD>(kg, p.k_ss, kb, klast, lane);
-    nv = ld_sub<kHD>(vg, p.v_ss, kb, klast, lane);
+    if constexpr (kPaged) {
+      nk = ld_kfrag_paged<kHD>(kg, p.pg, trow, p.k_sb, p.k_ss, kb, klast,
+                               lane);
+      nv = ld_sub_paged<kHD>(vg, p.pg, trow, p.v_sb, p.v_ss, kb, klast, lane);
+    } else {
+      nk = ld_kfrag<kHD>(kg, p.k_ss, kb, klast, lane);
+      nv = ld_sub<kHD>(vg, p.v_ss, kb, klast, lane);
+    }
   }
 
   for (; kb < kend; kb += 128) {
@@ -283,8 +360,15 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(
     // the next one's loads fly during this one's compute
     const int kn = kb + 128;
     if (kn < kend) {
-      nk = ld_kfrag<kHD>(kg, p.k_ss, kn, klast, lane);
-      nv = ld_sub<kHD>(vg, p.v_ss, kn, klast, lane);
+      if constexpr (kPaged) {
+        nk = ld_kfrag_paged<kHD>(kg, p.pg, trow, p.k_sb, p.k_ss, kn, klast,
+                                 lane);
+        nv = ld_sub_paged<kHD>(vg, p.pg, trow, p.v_sb, p.v_ss, kn, klast,
+                               lane);
+      } else {
+        nk = ld_kfrag<kHD>(kg, p.k_ss, kn, klast, lane);
+        nv = ld_sub<kHD>(vg, p.v_ss, kn, klast, lane);
+      }
     }
 
     // S^T tile: C[key][head] = sum_d K[key][d] * Q[head][d]
@@ -400,7 +484,12 @@ __global__ __launch_bounds__(64) void fa_decode_combine_kernel(
 template <int kHD>
 void launch_decode(const DecodeParams& p, dim3 grid, long BH,
                    hipStream_t stream) {
-  hipLaunchKernelGGL(fa_decode_kernel<kHD>, grid, dim3(256), 0, stream, p);
+  if (p.pg.table != nullptr)
+    hipLaunchKernelGGL((fa_decode_kernel<kHD, true>), grid, dim3(256), 0,
+                       stream, p);
+  else
+    hipLaunchKernelGGL((fa_decode_kernel<kHD, false>), grid, dim3(256), 0,
+                       stream, p);
   if (p.n_splits > 1)
     hipLaunchKernelGGL(fa_decode_combine_kernel<kHD>, dim3((unsigned)BH),
                        dim3(64), 0, stream, p.o_part, p.lse_part, p.out,
@@ -431,12 +520,19 @@ int fa_decode_splits(int B, int Hk, int Smax, int num_splits, int device) {
 // answered; above 1, o_part is fp32 [B, H, n_splits, head_dim] and lse_part
 // fp32 [B, H, n_splits]. k_new and v_new: both or neither; with them the
 // rows are appended at seqlens[b] first and attention covers one key more.
+// block_table: null, or int32 [B, max_pages] on the device; then k_cache and
+// v_cache are pools of n_pages pages of page_size rows, their strides are
+// (page, head, row) and Smax is max_pages * page_size.
 void fa_decode(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const void* k_new, const void* v_new,
                void* out, float* lse, float* o_part, float* lse_part, int B,
                int H, int Hk, int Smax, int head_dim, const long* strides,
-               float scale, int n_splits, int device, hipStream_t stream) {
+               float scale, int n_splits, const int* block_table,
+               int n_pages, int page_size, int max_pages, int device,
+               hipStream_t stream) {
   decode_check_shapes("fa_decode", B, H, Hk, Smax, head_dim);
+  const PageMap pages = make_page_map("fa_decode", block_table, n_pages,
+                                      page_size, max_pages, Smax);
   if (q == nullptr || k_cache == nullptr || v_cache == nullptr ||
       seqlens == nullptr || out == nullptr)
     throw std::runtime_error("fa_decode: null pointer");
@@ -476,13 +572,14 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
   p.lse_part = lse_part;
   p.out = (__bf16*)out;
   p.lse = lse;
+  p.pg = pages;
 
   if (k_new != nullptr) {
     // one new row per sequence: Sq = 1, no q_lens, row strides 0
     const long new_strides[6] = {strides[8],  strides[9],  0,
                                  strides[10], strides[11], 0};
     fa_cache_append(k_cache, v_cache, k_new, v_new, seqlens, nullptr,
-                    strides + 2, new_strides, B, Hk, 1, Smax, head_dim,
+                    strides + 2, new_strides, B, Hk, 1, Smax, head_dim, pages,
                     stream);
   }
   const dim3 grid(n_splits, Hk, B);

@@ -49,6 +49,27 @@ inline void decode_check_shapes(const char* name, long B, long H, long Hk,
     throw std::runtime_error(n + ": shape too large");
 }
 
+// A paged cache: n_pages pages of page_size key rows, max_pages table entries
+// per sequence. The kernels split a row index with a shift and a mask, so a
+// page is a power of two, and at least the 16 rows of an MFMA operand
+// fragment; the capacity max_pages * page_size obeys decode_check_shapes'
+// bound on Smax. Returns log2(page_size).
+inline int paged_check_shapes(const char* name, long n_pages, long page_size,
+                              long max_pages) {
+  const std::string n(name);
+  if (page_size < 16 || (page_size & (page_size - 1)) != 0)
+    throw std::runtime_error(n + ": the page size must be a power of two "
+                             ">= 16, got " + std::to_string(page_size));
+  if (n_pages < 1 || max_pages < 1)
+    throw std::runtime_error(n + ": empty page pool or block table");
+  if (page_size > (1L << 30) || max_pages > (1L << 30) / page_size ||
+      n_pages > (1L << 30))
+    throw std::runtime_error(n + ": paged shape too large");
+  int lg = 4;
+  while ((1L << lg) < page_size) ++lg;
+  return lg;
+}
+
 // Splits of a cache of capacity Smax for a launch that has `groups`
 // workgroups before any split. `requested` <= 0 is the policy: enough splits
 // that groups * n_splits workgroups fill the chip wg_per_cu times over, at

@@ -77,6 +77,28 @@
 //    weights the rest by exp(lse_s - lse_tot) in fp32, rounds once to bf16
 //    through out's strides; a row with only -inf splits gets zeros and -inf.
 //  * No atomics, no counters: deterministic.
+//  * Paged cache (block_table != null; the kPaged instantiations): k_cache
+//    and v_cache are pools [N, Hk, P, D], logical key row j of sequence b is
+//    row j & (P - 1) of page table[b, j >> log2 P], and Smax = max_pages * P
+//    feeds the clamps, the append's drop and the split plan. Paging changes
+//    addresses only: the tile walk, masking, partials and combine are the
+//    code above, so the output bits are those of the unpaged call on the
+//    gathered slab. Every address goes through attn_cache.h's paged_offset,
+//    after the row's clamp to total_b - 1 (no entry past a sequence's pages
+//    is read) and with the entry clamped to [0, N - 1]. The staging threads
+//    load rows srow and srow + 32 of a 64-key tile: with P >= 64 the tile
+//    lies in one page and the lookup is one scalar load per tile, by the
+//    tile's first key; with P 16 or 32 each thread looks up its two rows.
+//    The lookup is a dependent load in front of the next tile's prefetch,
+//    which the double buffer is left to hide: the entry for tile t + 2 is
+//    not fetched ahead (not tried). Measured (profiles/attn_paged.txt,
+//    contiguous / paged at P 16, 64, 256, us, two timings of one code within
+//    0.3 %): B1 Sq 8 H16 Hk4 D128 over 16384 45.0 / 49.1, 47.8, 48.0; B8 Sq
+//    512 H12 D64 over 3584 111 / 119, 116, 116. So the double buffer does
+//    not hide all of it: 4 to 9 %, most at P 16 with its two vector lookups
+//    a thread (reasoning, not a trace); against gathering the pages first (99 and 199 us) it is 1.7x
+//    to 2x faster. The kPaged = false code is the parent's: its times
+//    differ from a build of the parent by what two runs of one build do.
 //
 // Split policy, measured on one MI355X (256 CUs) with benchmarks/
 // attn_bench.py --shape extend --sweep (profiles/attn_extend_split.txt: host
@@ -108,7 +130,9 @@
 // VGPRs, 32 KB LDS, 4 waves/SIMD by registers (three workgroups per CU
 // asked for); head_dim 128 198 VGPRs, 64 KB LDS, 2 waves/SIMD; the split
 // instantiations 120 and 196 VGPRs with the same LDS; the combine kernel 18
-// and 19 VGPRs, no LDS; no scratch anywhere.
+// and 19 VGPRs, no LDS; the paged instantiations 118 and 194 VGPRs, split
+// 122 and 198, the same LDS and occupancy; the append kernel 18 VGPRs, paged
+// 20; no scratch anywhere.
 //
 // Build: ops/build.py compiles this file with the packed fp32 VALU forms
 // off (-packed-fp32-ops), the rule for new kernel files (STATUS.md, "Known
@@ -153,6 +177,7 @@ struct ExtendParams {
   int n_splits, L;           // key splits of a row tile, keys per split
   float* o_part;             // [B, H, Sq, n_splits, D]   n_splits > 1
   float* lse_part;           // [B, H, Sq, n_splits]      n_splits > 1
+  PageMap pg;                // kPaged: k, v are pools, k_sb, v_sb page strides
 };
 
 // Staging: 256 threads copy a [64 keys][kHD] tile from global to LDS. Thread
@@ -178,6 +203,34 @@ __device__ __forceinline__ RowTile<kHD> ld_tile(const __bf16* g, long ss,
   return t;
 }
 
+// kPaged: the same two rows of a tile whose first key is kt, found through
+// the block table (attn_cache.h). r0 and r1 are clamped to the sequence's
+// last key, which lies in the tile or past it, so they stay inside the tile:
+// with 64 rows or more to a page the tile lies in one page and one
+// wave-uniform (scalar) lookup by kt serves all lanes; with 16 or 32 each
+// lane looks up its own two rows.
+template <int kHD>
+__device__ __forceinline__ RowTile<kHD> ld_tile_paged(
+    const __bf16* g, const PageMap& pm, const int* trow, long sp, long ss,
+    int kt, int r0, int r1, int scol) {
+  long o0, o1;
+  if (pm.lg >= 6) {
+    o0 = paged_offset_in(pm, trow, kt, r0, sp, ss);
+    o1 = paged_offset_in(pm, trow, kt, r1, sp, ss);
+  } else {
+    o0 = paged_offset(pm, trow, r0, sp, ss);
+    o1 = paged_offset(pm, trow, r1, sp, ss);
+  }
+  RowTile<kHD> t;
+#pragma unroll
+  for (int blk = 0; blk < kHD / 64; ++blk) {
+    t.x[2 * blk] = *reinterpret_cast<const uint4*>(g + o0 + blk * 64 + scol);
+    t.x[2 * blk + 1] =
+        *reinterpret_cast<const uint4*>(g + o1 + blk * 64 + scol);
+  }
+  return t;
+}
+
 template <int kHD>
 __device__ __forceinline__ void st_tile(char* im, int srow, int scol,
                                         const RowTile<kHD>& t) {
@@ -195,8 +248,10 @@ __device__ __forceinline__ void st_tile(char* im, int srow, int scol,
 // rows r0 + 32 w .. + 31 of K/V head blockIdx.y. kSplit: grid.x is row tile *
 // n_splits + split, the workgroup walks keys [split * L, (split + 1) * L)
 // only and stores fp32 partials; the arithmetic of a tile is the same.
+// kPaged: K and V rows come from a page pool through the block table; only
+// the two staging loads differ.
 // ---------------------------------------------------------------------------
-template <int kHD, bool kSplit>
+template <int kHD, bool kSplit, bool kPaged>
 __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
     ExtendParams p) {
   static_assert(kHD == 64 || kHD == 128, "head_dim 64 or 128");
@@ -266,8 +321,13 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
     for (int c = 0; c < kNC; ++c)
       qf[c] = *reinterpret_cast<const bf16x8*>(qrow + c * 16 + hi * 8);
 
-    const __bf16* kg = p.k + (long)b * p.k_sb + (long)hk * p.k_sh;
-    const __bf16* vg = p.v + (long)b * p.v_sb + (long)hk * p.v_sh;
+    // paged: the head's plane of the pool; the page comes per tile or row
+    const __bf16* kg =
+        p.k + (kPaged ? 0 : (long)b * p.k_sb) + (long)hk * p.k_sh;
+    const __bf16* vg =
+        p.v + (kPaged ? 0 : (long)b * p.v_sb) + (long)hk * p.v_sh;
+    [[maybe_unused]] const int* trow =
+        kPaged ? p.pg.table + (long)b * p.pg.max_pages : nullptr;
     const int klast = total - 1;    // >= 0 here; loads never go past it
 
     float m = kNegBig, ssum = 0.f;
@@ -282,12 +342,23 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
     const int n64 = (kSplit ? min(kmax, k0 + p.L - 1) : kmax) / 64 + 1;
 
     // prologue: stage the first tile
-    st_tile<kHD>(kimg, srow, scol,
-                 ld_tile<kHD>(kg, p.k_ss, min(k0 + srow, klast),
-                              min(k0 + srow + 32, klast), scol));
-    st_tile<kHD>(vimg, srow, scol,
-                 ld_tile<kHD>(vg, p.v_ss, min(k0 + srow, klast),
-                              min(k0 + srow + 32, klast), scol));
+    if constexpr (kPaged) {
+      const int kr0 = min(k0 + srow, klast);
+      const int kr1 = min(k0 + srow + 32, klast);
+      st_tile<kHD>(kimg, srow, scol,
+                   ld_tile_paged<kHD>(kg, p.pg, trow, p.k_sb, p.k_ss, k0, kr0,
+                                      kr1, scol));
+      st_tile<kHD>(vimg, srow, scol,
+                   ld_tile_paged<kHD>(vg, p.pg, trow, p.v_sb, p.v_ss, k0, kr0,
+                                      kr1, scol));
+    } else {
+      st_tile<kHD>(kimg, srow, scol,
+                   ld_tile<kHD>(kg, p.k_ss, min(k0 + srow, klast),
+                                min(k0 + srow + 32, klast), scol));
+      st_tile<kHD>(vimg, srow, scol,
+                   ld_tile<kHD>(vg, p.v_ss, min(k0 + srow, klast),
+                                min(k0 + srow + 32, klast), scol));
+    }
     __syncthreads();
 
     int cur = 0;
@@ -298,8 +369,15 @@ __global__ __launch_bounds__(256, kHD == 64 ? 3 : 2) void fa_extend_kernel(
       if (pref) {
         const int kr0 = min((t + 1) * 64 + srow, klast);
         const int kr1 = min((t + 1) * 64 + srow + 32, klast);
-        nk = ld_tile<kHD>(kg, p.k_ss, kr0, kr1, scol);
-        nv = ld_tile<kHD>(vg, p.v_ss, kr0, kr1, scol);
+        if constexpr (kPaged) {
+          nk = ld_tile_paged<kHD>(kg, p.pg, trow, p.k_sb, p.k_ss,
+                                  (t + 1) * 64, kr0, kr1, scol);
+          nv = ld_tile_paged<kHD>(vg, p.pg, trow, p.v_sb, p.v_ss,
+                                  (t + 1) * 64, kr0, kr1, scol);
+        } else {
+          nk = ld_tile<kHD>(kg, p.k_ss, kr0, kr1, scol);
+          nv = ld_tile<kHD>(vg, p.v_ss, kr0, kr1, scol);
+        }
       }
 
 #pragma unroll
@@ -483,16 +561,16 @@ __global__ __launch_bounds__(256) void fa_extend_combine_kernel(
   if (lane == 0 && lse != nullptr) lse[row] = tot;
 }
 
-template <int kHD>
+template <int kHD, bool kPaged>
 void launch_extend(const ExtendParams& p, long row_tiles, int Hk, int B,
                    hipStream_t stream) {
   if (p.n_splits == 1) {
-    hipLaunchKernelGGL((fa_extend_kernel<kHD, false>),
+    hipLaunchKernelGGL((fa_extend_kernel<kHD, false, kPaged>),
                        dim3((unsigned)row_tiles, Hk, B), dim3(256), 0, stream,
                        p);
     return;
   }
-  hipLaunchKernelGGL((fa_extend_kernel<kHD, true>),
+  hipLaunchKernelGGL((fa_extend_kernel<kHD, true, kPaged>),
                      dim3((unsigned)(row_tiles * p.n_splits), Hk, B),
                      dim3(256), 0, stream, p);
   const long rows = (long)B * p.H * p.Sq;
@@ -515,8 +593,10 @@ struct AppendParams {
   long k_sb, k_sh, k_ss, v_sb, v_sh, v_ss;
   long kn_sb, kn_sh, kn_ss, vn_sb, vn_sh, vn_ss;
   int Sq, Smax, D;
+  PageMap pg;  // kPaged: k, v are pools, k_sb, v_sb their page strides
 };
 
+template <bool kPaged>
 __global__ __launch_bounds__(256) void fa_cache_append_kernel(
     AppendParams p) {
   const int hk = blockIdx.y, b = blockIdx.z;
@@ -527,6 +607,26 @@ __global__ __launch_bounds__(256) void fa_cache_append_kernel(
   const int piece = e - i * 2 * per;
   const int row = sl.past + i;
   if (i >= sl.n || row >= p.Smax) return;
+  if constexpr (kPaged) {
+    // 0 <= row < max_pages * P: the entry is one of the table row's
+    const int* trow = p.pg.table + (long)b * p.pg.max_pages;
+    if (piece < per)
+      *reinterpret_cast<uint4*>(
+          p.k + (long)hk * p.k_sh +
+          paged_offset(p.pg, trow, row, p.k_sb, p.k_ss) + piece * 8) =
+          *reinterpret_cast<const uint4*>(p.kn + (long)b * p.kn_sb +
+                                          (long)hk * p.kn_sh +
+                                          (long)i * p.kn_ss + piece * 8);
+    else
+      *reinterpret_cast<uint4*>(
+          p.v + (long)hk * p.v_sh +
+          paged_offset(p.pg, trow, row, p.v_sb, p.v_ss) + (piece - per) * 8) =
+          *reinterpret_cast<const uint4*>(p.vn + (long)b * p.vn_sb +
+                                          (long)hk * p.vn_sh +
+                                          (long)i * p.vn_ss +
+                                          (piece - per) * 8);
+    return;
+  }
   if (piece < per)
     *reinterpret_cast<uint4*>(p.k + (long)b * p.k_sb + (long)hk * p.k_sh +
                               (long)row * p.k_ss + piece * 8) =
@@ -551,7 +651,7 @@ void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
                      const void* v_new, const int* seqlens, const int* q_lens,
                      const long* cache_strides, const long* new_strides, int B,
                      int Hk, int Sq, int Smax, int head_dim,
-                     hipStream_t stream) {
+                     const PageMap& pages, hipStream_t stream) {
   AppendParams a = {};
   a.k = (__bf16*)k_cache;
   a.v = (__bf16*)v_cache;
@@ -568,10 +668,15 @@ void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
   a.Sq = Sq;
   a.Smax = Smax;
   a.D = head_dim;
+  a.pg = pages;
   const long pieces = (long)Sq * (head_dim / 4);
-  hipLaunchKernelGGL(fa_cache_append_kernel,
-                     dim3((unsigned)((pieces + 255) / 256), Hk, B), dim3(256),
-                     0, stream, a);
+  const dim3 grid((unsigned)((pieces + 255) / 256), Hk, B);
+  if (pages.table != nullptr)
+    hipLaunchKernelGGL(fa_cache_append_kernel<true>, grid, dim3(256), 0,
+                       stream, a);
+  else
+    hipLaunchKernelGGL(fa_cache_append_kernel<false>, grid, dim3(256), 0,
+                       stream, a);
 }
 
 // The split count the policy (num_splits <= 0) or the caller (>= 1) gets for
@@ -595,13 +700,19 @@ int fa_extend_splits(int B, int Hk, int Sq, int G, int Smax, int num_splits,
 // 1, o_part is fp32 [B, H, Sq, n_splits, head_dim] and lse_part fp32
 // [B, H, Sq, n_splits], neither initialised. device: the tensors' device
 // index, made current for the call; `stream` is one of its streams.
+// block_table: null, or int32 [B, max_pages] on the device; then k_cache and
+// v_cache are pools of n_pages pages of page_size rows, their strides are
+// (page, head, row) and Smax is max_pages * page_size.
 void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
                int Sq, int Smax, int head_dim, const long* strides,
                float scale, bool causal, int n_splits, float* o_part,
-               float* lse_part, int device, hipStream_t stream) {
+               float* lse_part, const int* block_table, int n_pages,
+               int page_size, int max_pages, int device, hipStream_t stream) {
   decode_check_shapes("fa_extend", B, H, Hk, Smax, head_dim);
+  const PageMap pages = make_page_map("fa_extend", block_table, n_pages,
+                                      page_size, max_pages, Smax);
   const long G = H / Hk;
   // group rows and the append's piece index stay inside int arithmetic
   if (Sq < 1 || (long)Sq * G > (1L << 30) ||
@@ -651,15 +762,19 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
   p.L = plan.L;
   p.o_part = o_part;
   p.lse_part = lse_part;
+  p.pg = pages;
 
   if (k_new != nullptr)
     fa_cache_append(k_cache, v_cache, k_new, v_new, seqlens, q_lens,
                     strides + 3, strides + 12, B, Hk, Sq, Smax, head_dim,
-                    stream);
+                    pages, stream);
+  const bool paged = pages.table != nullptr;
   if (head_dim == 64)
-    launch_extend<64>(p, row_tiles, Hk, B, stream);
+    paged ? launch_extend<64, true>(p, row_tiles, Hk, B, stream)
+          : launch_extend<64, false>(p, row_tiles, Hk, B, stream);
   else
-    launch_extend<128>(p, row_tiles, Hk, B, stream);
+    paged ? launch_extend<128, true>(p, row_tiles, Hk, B, stream)
+          : launch_extend<128, false>(p, row_tiles, Hk, B, stream);
 }
 
 }  // namespace adapcc

@@ -127,13 +127,16 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const void* k_new, const void* v_new,
                void* out, float* lse, float* o_part, float* lse_part, int B,
                int H, int Hk, int Smax, int head_dim, const long* strides,
-               float scale, int n_splits, int device, hipStream_t stream);
+               float scale, int n_splits, const int* block_table,
+               int n_pages, int page_size, int max_pages, int device,
+               hipStream_t stream);
 void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
                int Sq, int Smax, int head_dim, const long* strides,
                float scale, bool causal, int n_splits, float* o_part,
-               float* lse_part, int device, hipStream_t stream);
+               float* lse_part, const int* block_table, int n_pages,
+               int page_size, int max_pages, int device, hipStream_t stream);
 int fa_extend_splits(int B, int Hk, int Sq, int G, int Smax, int num_splits,
                      int device);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
@@ -419,7 +422,10 @@ PYBIND11_MODULE(_core, m) {
   // [B,H,n_splits] are the workspaces. k_new, v_new != 0: the rows are
   // appended at seqlens[b] first. device: the tensors' device index, made
   // current for the call (stream is one of its streams). Nothing reads
-  // seqlens on the host.
+  // seqlens on the host. block_table != 0 (int32 [B,max_pages] on the
+  // device): the caches are pools [n_pages,Hk,page_size,head_dim], their
+  // strides (page, h, row), and Smax = max_pages * page_size; likewise for
+  // fa_extend.
   m.def("fa_decode_splits", &adapcc::fa_decode_splits, py::arg("B"),
         py::arg("Hk"), py::arg("Smax"), py::arg("num_splits"),
         py::arg("device"));
@@ -429,14 +435,17 @@ PYBIND11_MODULE(_core, m) {
            int head_dim, const std::vector<long>& strides, float scale,
            int n_splits, int device, uintptr_t stream, uintptr_t k_new,
            uintptr_t v_new, uintptr_t lse, uintptr_t o_part,
-           uintptr_t lse_part) {
+           uintptr_t lse_part, uintptr_t block_table, int n_pages,
+           int page_size, int max_pages) {
           if (strides.size() != 12)
             throw std::runtime_error("fa_decode: need 12 strides");
           adapcc::fa_decode((const void*)q, (void*)k_cache, (void*)v_cache,
                             (const int*)seqlens, (const void*)k_new,
                             (const void*)v_new, (void*)out, (float*)lse,
                             (float*)o_part, (float*)lse_part, B, H, Hk, Smax,
-                            head_dim, strides.data(), scale, n_splits, device,
+                            head_dim, strides.data(), scale, n_splits,
+                            (const int*)block_table, n_pages, page_size,
+                            max_pages, device,
                             reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
@@ -446,7 +455,9 @@ PYBIND11_MODULE(_core, m) {
         py::arg("Hk"), py::arg("Smax"), py::arg("head_dim"),
         py::arg("strides"), py::arg("scale"), py::arg("n_splits"),
         py::arg("device"), py::arg("stream"), py::arg("k_new") = 0, py::arg("v_new") = 0,
-        py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0);
+        py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0,
+        py::arg("block_table") = 0, py::arg("n_pages") = 0,
+        py::arg("page_size") = 0, py::arg("max_pages") = 0);
   // Multi-row attention over a KV cache (attn_extend.hip). q and out
   // [B,H,Sq,head_dim], caches [B,Hk,Smax,head_dim], seqlens int32 [B] on the
   // device, q_lens int32 [B] or 0, lse fp32 [B,H,Sq] or 0. strides: q,
@@ -466,7 +477,8 @@ PYBIND11_MODULE(_core, m) {
            float scale, bool causal, int device, uintptr_t stream,
            uintptr_t q_lens, uintptr_t k_new, uintptr_t v_new,
            uintptr_t lse, int n_splits, uintptr_t o_part,
-           uintptr_t lse_part) {
+           uintptr_t lse_part, uintptr_t block_table, int n_pages,
+           int page_size, int max_pages) {
           if (strides.size() != 18)
             throw std::runtime_error("fa_extend: need 18 strides");
           adapcc::fa_extend((const void*)q, (void*)k_cache, (void*)v_cache,
@@ -474,7 +486,9 @@ PYBIND11_MODULE(_core, m) {
                             (const void*)k_new, (const void*)v_new,
                             (void*)out, (float*)lse, B, H, Hk, Sq, Smax,
                             head_dim, strides.data(), scale, causal, n_splits,
-                            (float*)o_part, (float*)lse_part, device,
+                            (float*)o_part, (float*)lse_part,
+                            (const int*)block_table, n_pages, page_size,
+                            max_pages, device,
                             reinterpret_cast<hipStream_t>(stream));
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
@@ -486,7 +500,9 @@ PYBIND11_MODULE(_core, m) {
         py::arg("device"), py::arg("stream"), py::arg("q_lens") = 0,
         py::arg("k_new") = 0, py::arg("v_new") = 0, py::arg("lse") = 0,
         py::arg("n_splits") = 1, py::arg("o_part") = 0,
-        py::arg("lse_part") = 0);
+        py::arg("lse_part") = 0, py::arg("block_table") = 0,
+        py::arg("n_pages") = 0, py::arg("page_size") = 0,
+        py::arg("max_pages") = 0);
   m.def("mfma_probe",
         [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t stream) {
           adapcc::mfma_probe((const void*)a, (const void*)b, (float*)c,

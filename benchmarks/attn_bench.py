@@ -98,8 +98,16 @@ def main():
     ap.add_argument("--kv-heads", type=int, default=0,
                     help="K/V heads (must divide the shape's heads): the "
                          "grouped-query comparison instead of the usual one")
+    ap.add_argument("--page-size", type=int, default=0,
+                    help="decode and extend: time a paged cache of this page "
+                         "size (a power of two >= 16) against the contiguous "
+                         "one instead")
     args = ap.parse_args()
     drop = args.dropout
+    if args.page_size:
+        if args.shape not in ("decode", "extend"):
+            ap.error("--page-size goes with --shape decode or extend")
+        return paged_path(args.shape, args.page_size)
     if args.shape == "decode":
         return decode_path(args.head_dim, args.kv_heads, args.sweep)
     if args.shape == "extend":
@@ -251,6 +259,75 @@ def decode_path(D, kv_heads, sweep):
                           f"{nbytes / ms / 1e9:6.2f} TB/s  "
                           f"this/decode {ms / base:.2f}")
                 del q, k, v, mask, ref
+
+
+def paged_path(shape, P):
+    """--page-size: the paged call (a pool [N,Hk,P,D] under a shuffled block
+    table) against the contiguous call on the same keys, alternating in one
+    process, at the shapes the kernel headers quote. 'contiguous again' is
+    the first candidate a second time: what two timings of one code differ
+    by. 'gather + contiguous' is what a caller with pages had to do before
+    block_table: build the slab, then call."""
+    from adapcc_amd.ops.attention import (fa_decode_supported,
+                                          fa_extend_supported,
+                                          flash_attention_decode,
+                                          flash_attention_extend)
+
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+    decode = shape == "decode"
+    cases = (((32, 16, 4, 128, 1, 16383), (1, 16, 16, 128, 1, 16383))
+             if decode else
+             ((1, 16, 4, 128, 8, 16384), (8, 12, 12, 64, 512, 3584)))
+    for B, H, Hk, D, Sq, past in cases:
+        torch.manual_seed(0)
+        mp = -(-(past + Sq) // P)
+        Smax = mp * P
+        q = torch.randn(B, H, Sq, D, **bf)
+        k = torch.randn(B, Hk, Smax, D, **bf)
+        v = torch.randn_like(k)
+        lens = torch.full((B,), past + Sq, dtype=torch.int32, device="cuda")
+        table = torch.randperm(B * mp, device="cuda").view(B, mp).int()
+        tl = table.long()
+        pools = []
+        for t in (k, v):
+            pool = torch.empty(B * mp, Hk, P, D, **bf)
+            pool[tl.view(-1)] = t.view(B, Hk, mp, P, D).transpose(
+                1, 2).reshape(-1, Hk, P, D)
+            pools.append(pool)
+        kp, vp = pools
+
+        def call(kc, vc, **kw):
+            if decode:
+                return flash_attention_decode(q[:, :, 0], kc, vc, lens, **kw)
+            return flash_attention_extend(q, kc, vc, lens, **kw)
+
+        def gather():
+            return call(*(t[tl].transpose(1, 2).reshape(B, Hk, Smax, D)
+                          for t in (kp, vp)))
+
+        # a missing kernel is an error, not a silent composed-route run
+        assert (fa_decode_supported(q[:, :, 0], kp, vp, lens,
+                                    block_table=table) if decode else
+                fa_extend_supported(q, kp, vp, lens, block_table=table))
+        assert torch.equal(call(k, v), call(kp, vp, block_table=table))
+        assert torch.equal(call(k, v), gather())
+        fns = {
+            "contiguous": lambda: call(k, v),
+            f"paged P={P}": lambda: call(kp, vp, block_table=table),
+            "contiguous again": lambda: call(k, v),
+            "gather + contiguous": gather,
+        }
+        nbytes = 2 * B * Hk * Smax * D * 2
+        print(f"{shape} B{B} H{H} Hk{Hk} D{D} Sq{Sq} keys{past + Sq} P{P} "
+              f"({mp} pages a sequence, K/V {nbytes / 2**20:.1f} MiB)")
+        base = None
+        for name, (ms, lo, hi) in alternate(fns, window=0.3).items():
+            base = base or ms
+            print(f"  {name:<22} {ms * 1e3:9.1f} us  (rounds "
+                  f"{lo * 1e3:.1f}..{hi * 1e3:.1f})  "
+                  f"{nbytes / ms / 1e9:6.2f} TB/s  "
+                  f"this/contiguous {ms / base:.3f}")
+        del q, k, v, kp, vp, pools
 
 
 def extend_path(D, kv_heads, sweep):
