@@ -83,6 +83,19 @@ never read on the host, and memory grows with the tokens held, sequences of
 any lengths share one pool and a common prefix is stored once. P must be a
 power of two >= 16 there; ``_paged_composed`` (gather, compose, write the
 appended rows back) is the route for everything else and the definition.
+
+Decode also takes an FP8 cache: k_cache and v_cache (slabs or pools) of
+``torch.float8_e4m3fn`` with per-head ``k_scale``, ``v_scale`` (fp32 [Hk] on
+the device), a stored byte c of head hk standing for float(c) * scale[hk].
+Half the memory per key and half the bytes a step reads, which is what
+bounds decode. The kernels (csrc/attn_decode_fp8.hip) load the bytes in a
+layout of their own, dequantise in registers (e4m3 -> bf16 is exact) into
+the bf16 MFMA path, and fold the scales into the softmax scale and the final
+normalisation; q, the new rows and the output stay bf16. Rows are quantised
+when they are written, by one function, ``kv_quantize_reference``
+(divide, clamp to +-448, round to nearest even): by decode's own append and
+by ``kv_cache_append``, the append step alone, which is how a bf16 prefill
+fills such a cache. ``flash_attention_extend`` does not take e4m3 caches.
 """
 
 from __future__ import annotations
@@ -100,7 +113,8 @@ __all__ = ["flash_attention", "flash_attention_qkv", "fa_supported",
            "flash_attention_qkv_varlen", "fa_varlen_supported",
            "fa_qkv_varlen_supported", "varlen_tile_map_reference",
            "flash_attention_decode", "fa_decode_supported",
-           "flash_attention_extend", "fa_extend_supported"]
+           "flash_attention_extend", "fa_extend_supported",
+           "kv_cache_append", "kv_quantize_reference"]
 
 
 _QT = 128  # rows per workgroup tile, csrc/attn.hip's kQT
@@ -128,8 +142,10 @@ def _row_ok(t: torch.Tensor) -> bool:
         return False
     if t.data_ptr() % 16 != 0:
         return False
-    # every row/plane base must stay 16-B aligned (bf16: 8 elements)
-    return all(s % 8 == 0 for s in t.stride()[:-1])
+    # every row/plane base must stay 16-B aligned (bf16: 8 elements; one-byte
+    # elements, the e4m3 caches: 16)
+    step = 16 if t.element_size() == 1 else 8
+    return all(s % step == 0 for s in t.stride()[:-1])
 
 
 def _kernel_ok(t: torch.Tensor, D: int, S: int, causal: bool,
@@ -717,12 +733,19 @@ _DECODE_MAX_GROUP = 32  # csrc/attn_decode_plan.h's kDecodeMaxGroup
 _PAGED_MAX_KEYS = 1 << 30   # its bound on Smax, for max_pages * P
 
 
+def _is_fp8(k_cache, v_cache) -> bool:
+    return k_cache.dtype == v_cache.dtype == torch.float8_e4m3fn
+
+
 def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                  q_lens=None, block_table=None) -> None:
+                  q_lens=None, block_table=None, k_scale=None, v_scale=None,
+                  fp8_ok=False) -> None:
     """The argument checks of the calls over a KV cache. q is [B,H,D]
     (decode) or [B,H,Sq,D] (extend), new rows then [B,Hk,D] or [B,Hk,Sq,D];
     q_lens (extend) like cache_seqlens. With block_table (int32
-    [B,max_pages]) the caches are page pools [N,Hk,P,D]."""
+    [B,max_pages]) the caches are page pools [N,Hk,P,D]. fp8_ok (decode and
+    ``kv_cache_append``): e4m3 caches under a q of another float dtype are
+    taken, with k_scale and v_scale, fp32 [Hk]."""
     rows = "" if name.endswith("decode") else "Sq,"
     paged = block_table is not None
     form = "[N,Hk,P,D]" if paged else "[B,Hk,Smax,D]"
@@ -758,9 +781,20 @@ def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
     if H % Hk != 0:
         raise ValueError(f"{name}: the K/V head count must divide q's, got "
                          f"{H} and {Hk}")
-    if not (q.dtype == k_cache.dtype == v_cache.dtype):
+    if (fp8_ok and _is_fp8(k_cache, v_cache) and q.is_floating_point()
+            and q.element_size() > 1):
+        for n, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
+                    or t.shape != (Hk,) or not t.is_contiguous()
+                    or t.device != q.device):
+                raise ValueError(f"{name}: an e4m3 cache needs {n}, fp32 "
+                                 f"[Hk] = [{Hk}], contiguous, on {q.device}")
+    elif not (q.dtype == k_cache.dtype == v_cache.dtype):
         raise ValueError(f"{name}: q and the caches must have one dtype, got "
                          f"{q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError(f"{name}: k_scale and v_scale go with e4m3 "
+                         f"(torch.float8_e4m3fn) caches, got {k_cache.dtype}")
     if not (q.device == k_cache.device == v_cache.device):
         raise ValueError(f"{name}: q and the caches must be on one device")
     for n, t in (("cache_seqlens", cache_seqlens), ("q_lens", q_lens)):
@@ -864,14 +898,18 @@ def _cached_launch_args(q, k_cache, k_new, v_new, return_lse,
 def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor,
                         cache_seqlens: torch.Tensor,
-                        block_table: Optional[torch.Tensor] = None) -> bool:
-    """True where ``flash_attention_decode`` runs its kernels: bf16 on the
+                        block_table: Optional[torch.Tensor] = None,
+                        k_scale: Optional[torch.Tensor] = None,
+                        v_scale: Optional[torch.Tensor] = None) -> bool:
+    """True where ``flash_attention_decode`` runs its kernels: bf16 q on the
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
     contiguous and 16-B aligned, extension built; with ``block_table`` also
-    a page size that is a power of two >= 16 and a contiguous table."""
+    a page size that is a power of two >= 16 and a contiguous table. The
+    caches are bf16, or e4m3 with ``k_scale`` and ``v_scale``."""
     try:
         _check_cached("flash_attention_decode", q, k_cache, v_cache,
-                      cache_seqlens, None, None, None, block_table)
+                      cache_seqlens, None, None, None, block_table, k_scale,
+                      v_scale, fp8_ok=True)
     except ValueError:
         return False
     return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, None,
@@ -879,9 +917,11 @@ def fa_decode_supported(q: torch.Tensor, k_cache: torch.Tensor,
 
 
 def _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
-                   num_splits, return_lse, block_table=None):
+                   num_splits, return_lse, block_table=None, k_scale=None,
+                   v_scale=None):
     """The kernel path, for arguments that passed ``_check_cached`` and
-    ``_cached_kernel_ok``."""
+    ``_cached_kernel_ok``. With the scales: e4m3 caches and the kernels of
+    csrc/attn_decode_fp8.hip."""
     core = _core()
     B, H, D = q.shape
     Hk = k_cache.shape[1]
@@ -899,10 +939,139 @@ def _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
         a.kw.update(o_part=o_part.data_ptr(), lse_part=lse_part.data_ptr())
     strides = ([q.stride(0), q.stride(1)] + _strides3(k_cache)
                + _strides3(v_cache) + a.new_strides)
-    core.fa_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                   cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Smax,
-                   D, strides, scale, ns, a.device, a.stream, **a.kw)
+    if k_scale is not None:
+        core.fa_decode_fp8(q.data_ptr(), k_cache.data_ptr(),
+                           v_cache.data_ptr(), cache_seqlens.data_ptr(),
+                           k_scale.data_ptr(), v_scale.data_ptr(),
+                           out.data_ptr(), B, H, Hk, Smax, D, strides, scale,
+                           ns, a.device, a.stream, **a.kw)
+    else:
+        core.fa_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                       cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk,
+                       Smax, D, strides, scale, ns, a.device, a.stream,
+                       **a.kw)
     return (out, a.lse) if return_lse else out
+
+
+# ---------------------------------------------------------------------------
+# FP8 (e4m3) caches: the quantisation function, the append step alone, and
+# decode off the kernel path
+# ---------------------------------------------------------------------------
+def kv_quantize_reference(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The one quantisation function of the e4m3 caches, in torch:
+    q8(x, s) = rne_e4m3(clamp(float(x) / s, -448, 448)) as
+    ``torch.float8_e4m3fn``. x has the K/V heads in dim 1, scale is [Hk]
+    (> 0). The clamp is part of the definition: without it a value past 448
+    becomes NaN. The append kernel (csrc/attn_decode_fp8.hip) computes the
+    same with an fp32 division."""
+    s = scale.float().view((1, -1) + (1,) * (x.dim() - 2))
+    return (x.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+
+
+def _append_composed(k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
+                     block_table) -> None:
+    """The append step off the kernel path: ``_paged_composed``'s write-back
+    (a masked rewrite through an inverse index, no host sync), a slab being
+    the pool of B pages of Smax rows under the table arange(B). One-byte
+    caches move as uint8: k_new, v_new are quantised already."""
+    B, Hk, Sq, D = k_new.shape
+    N, P = k_cache.shape[0], k_cache.shape[2]
+    dev = k_new.device
+    if block_table is None:
+        table = torch.arange(B, device=dev).view(B, 1)
+    else:
+        table = block_table.clamp(0, N - 1).long()
+    Smax = table.shape[1] * P
+    past = cache_seqlens.clamp(0, Smax).view(B, 1).long()
+    n = (torch.full_like(cache_seqlens, Sq) if q_lens is None
+         else q_lens.clamp(0, Sq)).view(B, 1)
+    i = torch.arange(Sq, device=dev).view(1, Sq)
+    row = past + i                                        # [B,Sq]
+    kept = (i < n) & (row < Smax)
+    row = row.clamp(max=Smax - 1)
+    slot = torch.where(kept, table.gather(1, row // P) * P + row % P, N * P)
+    inv = torch.full((N * P + 1,), -1, dtype=torch.long, device=dev)
+    inv.scatter_(0, slot.reshape(-1), torch.arange(B * Sq, device=dev))
+    inv = inv[:N * P].view(N, P)
+    hit = (inv >= 0).view(N, 1, P, 1)
+    for pool, new in ((k_cache, k_new), (v_cache, v_new)):
+        if pool.element_size() == 1:
+            pool, new = pool.view(torch.uint8), new.view(torch.uint8)
+        src = new.transpose(1, 2).reshape(B * Sq, Hk, D)
+        pool.copy_(torch.where(hit, src[inv.clamp(min=0)].transpose(1, 2),
+                               pool))
+
+
+def kv_cache_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                    cache_seqlens: torch.Tensor, k_new: torch.Tensor,
+                    v_new: torch.Tensor,
+                    q_lens: Optional[torch.Tensor] = None,
+                    block_table: Optional[torch.Tensor] = None,
+                    k_scale: Optional[torch.Tensor] = None,
+                    v_scale: Optional[torch.Tensor] = None) -> None:
+    """The append step of ``flash_attention_extend`` alone, in place: rows
+    i < n_b of k_new, v_new [B,Hk,Sq,D] go to logical cache rows past_b + i
+    (through ``block_table`` when the caches are pools), rows at or past
+    Smax are dropped, no other byte is written, the lengths are neither
+    modified nor read on the host. Caches of k_new's dtype take the rows as
+    they are; e4m3 caches (``torch.float8_e4m3fn``) need ``k_scale`` and
+    ``v_scale`` (fp32 [Hk]) and take ``kv_quantize_reference`` of them, so a
+    stored byte c of head hk stands for float(c) * scale[hk]. This is how a
+    prompt enters an e4m3 cache: prefill attention runs in bf16, its k and v
+    are appended here, and ``flash_attention_decode`` then steps over e4m3.
+    bf16 rows on the GPU run the append kernels (csrc/attn_extend.hip,
+    csrc/attn_decode_fp8.hip); anything else is composed in torch."""
+    name = "kv_cache_append"
+    if not isinstance(k_new, torch.Tensor) or k_new.dim() != 4:
+        raise ValueError(f"{name}: need k_new and v_new [B,Hk,Sq,D]")
+    _check_cached(name, k_new, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                  q_lens, block_table, k_scale, v_scale, fp8_ok=True)
+    if k_new.shape[1] != k_cache.shape[1]:
+        raise ValueError(f"{name}: k_new has {k_new.shape[1]} heads, the "
+                         f"caches {k_cache.shape[1]}")
+    _check_no_grad(name, k_cache, v_cache, k_new, v_new)
+    if _cached_kernel_ok(k_new, k_cache, v_cache, cache_seqlens, q_lens,
+                         block_table) and _row_ok(v_new):
+        B, Hk, Sq, D = k_new.shape
+        a = _cached_launch_args(k_new, k_cache, None, None, False,
+                                block_table)
+        if k_scale is not None:
+            a.kw.update(k_scale=k_scale.data_ptr(),
+                        v_scale=v_scale.data_ptr())
+        if q_lens is not None:
+            a.kw.update(q_lens=q_lens.data_ptr())
+        _core().fa_kv_append(
+            k_cache.data_ptr(), v_cache.data_ptr(), k_new.data_ptr(),
+            v_new.data_ptr(), cache_seqlens.data_ptr(), B, Hk, Sq, a.Smax, D,
+            _strides3(k_cache) + _strides3(v_cache),
+            _strides3(k_new) + _strides3(v_new), a.device, a.stream, **a.kw)
+        return
+    if k_scale is not None:
+        k_new = kv_quantize_reference(k_new, k_scale)
+        v_new = kv_quantize_reference(v_new, v_scale)
+    _append_composed(k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
+                     block_table)
+
+
+def _fp8_decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                         scale, return_lse, block_table, k_scale, v_scale):
+    """Decode over e4m3 caches off the kernel path, and its definition: the
+    new rows quantised and written, the caches dequantised to q's dtype,
+    then the composed route on those with no new rows and the lengths
+    advanced on the device."""
+    lens = cache_seqlens
+    if k_new is not None:
+        _append_composed(
+            k_cache, v_cache, cache_seqlens,
+            kv_quantize_reference(k_new.unsqueeze(2), k_scale),
+            kv_quantize_reference(v_new.unsqueeze(2), v_scale), None,
+            block_table)
+        lens = cache_seqlens.clamp(min=0) + 1     # clamped to Smax below
+    kd, vd = ((c.float() * s.view(1, -1, 1, 1)).to(q.dtype)
+              for c, s in ((k_cache, k_scale), (v_cache, v_scale)))
+    res = _extend_composed(q.unsqueeze(2), kd, vd, lens, None, None, None,
+                           True, scale, return_lse, block_table)
+    return (res[0][:, :, 0], res[1][:, :, 0]) if return_lse else res[:, :, 0]
 
 
 def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
@@ -913,7 +1082,9 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                            scale: float = None,
                            num_splits: Optional[int] = None,
                            return_lse: bool = False,
-                           block_table: Optional[torch.Tensor] = None):
+                           block_table: Optional[torch.Tensor] = None,
+                           k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None):
     """Attention of one new token per sequence over a KV cache. q: [B,H,D];
     k_cache, v_cache: [B,Hk,Smax,D] with H % Hk == 0 and any batch, head and
     row strides (a [B,Smax,Hk,D] cache goes in as its transposed view), query
@@ -939,9 +1110,23 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
 
     With ``block_table`` (int32 [B,max_pages]) the cache is paged: k_cache
     and v_cache are pools [N,Hk,P,D] and Smax = max_pages * P, as
-    ``flash_attention_extend`` describes."""
+    ``flash_attention_extend`` describes.
+
+    FP8 cache: k_cache and v_cache of dtype ``torch.float8_e4m3fn`` (slabs
+    or pools, rows 16-B aligned: leading strides multiples of 16) with
+    ``k_scale`` and ``v_scale``, fp32 [Hk] on the same device, positive: a
+    stored byte c of K/V head hk stands for float(c) * scale[hk]. q, k_new,
+    v_new and the output keep q's dtype; new rows are stored as
+    ``kv_quantize_reference`` of them, and lse is the logsumexp of the
+    scaled scores of the dequantised keys. The scales are read on the device
+    only. bf16 q runs the kernels of csrc/attn_decode_fp8.hip, which read
+    half the bytes and dequantise in registers (e4m3 -> bf16 is exact);
+    anything else quantises and writes the new rows, dequantises the caches
+    to q's dtype and composes as above. ``kv_cache_append`` fills such a
+    cache from a bf16 prefill."""
     _check_cached("flash_attention_decode", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new, None, block_table)
+                  cache_seqlens, k_new, v_new, None, block_table, k_scale,
+                  v_scale, fp8_ok=True)
     _check_no_grad("flash_attention_decode", q, k_cache, v_cache, k_new,
                    v_new)
     if num_splits is not None and int(num_splits) < 1:
@@ -951,7 +1136,12 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                          block_table):
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_decode(q, k_cache, v_cache, cache_seqlens, k_new,
-                              v_new, s, num_splits, return_lse, block_table)
+                              v_new, s, num_splits, return_lse, block_table,
+                              k_scale, v_scale)
+    if k_scale is not None:
+        return _fp8_decode_composed(q, k_cache, v_cache, cache_seqlens, k_new,
+                                    v_new, scale, return_lse, block_table,
+                                    k_scale, v_scale)
     # a block of one row; [B,1,H,D] memory, so the [B,H,D] result is contiguous
     one = [None if t is None else t.unsqueeze(2) for t in (q, k_new, v_new)]
     res = _extend_composed(one[0], k_cache, v_cache, cache_seqlens, one[1],

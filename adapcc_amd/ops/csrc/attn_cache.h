@@ -8,8 +8,11 @@
 // span from the finished score tile to the last PV MFMA. Decode calls it;
 // extend holds the same span written out (with an s_setprio pair), since as
 // a function call it got another register allocation and lost time at one
-// shape (profiles/README.md, "Shared header ..."). Compiled only through the
-// two files, so with their flags (ops/build.py: packed fp32 VALU forms off).
+// shape (profiles/README.md, "Shared header ..."). attn_decode_fp8.hip, decode
+// over an e4m3 cache, is a third user: the lengths, the page map, the tile
+// step, and decode's combine kernel through a host launcher. Compiled only
+// through these files, so with their flags (ops/build.py: packed fp32 VALU
+// forms off).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -85,6 +88,28 @@ __device__ __forceinline__ long paged_offset_in(const PageMap& pm,
                                                 long row_stride) {
   return page_base(pm, trow, urow, page_stride) +
          (long)(row & ((1 << pm.lg) - 1)) * row_stride;
+}
+
+// The decode kernels' lookup (attn_decode.hip, attn_decode_fp8.hip): where a
+// wave's loads find key row `row` (clamped to the split's last key, so
+// inside the sub-tile that starts at kb) of a page pool. kb is a multiple of
+// 32: with 32 rows or more to a page the sub-tile lies in one page and one
+// wave-uniform (scalar) lookup serves every lane; at 16 it lies in two and
+// each lane looks up its own row.
+__device__ __forceinline__ long paged_sub_offset(const PageMap& pm,
+                                                 const int* trow, int kb,
+                                                 int row, long sp, long ss) {
+  if (pm.lg >= 5)
+    return paged_offset_in(pm, trow, __builtin_amdgcn_readfirstlane(kb), row,
+                           sp, ss);
+  return paged_offset(pm, trow, row, sp, ss);
+}
+
+// Orders this wave's LDS writes and reads for the compiler; the hardware
+// serves one wave's LDS instructions in order.
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // Four f32 -> four bf16 (round to nearest even), one 8-byte store.
@@ -188,6 +213,25 @@ void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
                      const long* cache_strides, const long* new_strides, int B,
                      int Hk, int Sq, int Smax, int head_dim,
                      const PageMap& pages, hipStream_t stream);
+
+// The same for e4m3 caches (attn_decode_fp8.hip): the bf16 rows are written
+// as q8(x, s) = rne_e4m3(clamp(float(x) / s, -448, 448)) with s = k_scale[hk]
+// or v_scale[hk] (fp32 [Hk] on the device), and the cache strides count
+// bytes.
+void fa_cache_append_fp8(void* k_cache, void* v_cache, const void* k_new,
+                         const void* v_new, const int* seqlens,
+                         const int* q_lens, const float* k_scale,
+                         const float* v_scale, const long* cache_strides,
+                         const long* new_strides, int B, int Hk, int Sq,
+                         int Smax, int head_dim, const PageMap& pages,
+                         hipStream_t stream);
+
+// Decode's merge of the key splits (attn_decode.hip's combine kernel): o_part
+// fp32 [BH, n_splits, head_dim] normalised partials and lse_part fp32
+// [BH, n_splits] to out bf16 [BH, head_dim] and lse fp32 [BH] (or null).
+void fa_decode_combine(const float* o_part, const float* lse_part, void* out,
+                       float* lse, int n_splits, long BH, int head_dim,
+                       hipStream_t stream);
 
 // The PageMap of a host call, checked (attn_decode_plan.h): block_table null
 // is the unpaged call and gives table == nullptr; else Smax must be

@@ -153,20 +153,6 @@ struct DecodeParams {
   PageMap pg;               // kPaged: k, v are pools, k_sb, v_sb page strides
 };
 
-// kPaged: where a wave's loads find key row `row` (clamped to the split's
-// last key, so inside the sub-tile that starts at kb) of a page pool. kb is
-// a multiple of 32: with 32 rows or more to a page the sub-tile lies in one
-// page and one wave-uniform (scalar) lookup serves every lane; at 16 it
-// lies in two and each lane looks up its own row.
-__device__ __forceinline__ long paged_sub_offset(const PageMap& pm,
-                                                 const int* trow, int kb,
-                                                 int row, long sp, long ss) {
-  if (pm.lg >= 5)
-    return paged_offset_in(pm, trow, __builtin_amdgcn_readfirstlane(kb), row,
-                           sp, ss);
-  return paged_offset(pm, trow, row, sp, ss);
-}
-
 // One wave's share of a [32 keys][kHD] sub-tile: per 64-column block, lane t
 // moves the 16 B at column (t&7)*8 of rows (t>>3) + 8*i, i = 0..3, so every
 // load instruction covers eight whole 128-B rows.
@@ -253,13 +239,6 @@ __device__ __forceinline__ KFrag<kHD> ld_kfrag_paged(
   for (int c = 0; c < kHD / 16; ++c)
     t.f[c] = *reinterpret_cast<const bf16x8*>(r + c * 16);
   return t;
-}
-
-// Orders this wave's LDS writes and reads for the compiler; the hardware
-// serves one wave's LDS instructions in order.
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 // ---------------------------------------------------------------------------
@@ -501,6 +480,21 @@ void launch_decode(const DecodeParams& p, dim3 grid, long BH,
 // ---------------------------------------------------------------------------
 // Host side (bound in bindings.hip). Nothing here reads the lengths.
 // ---------------------------------------------------------------------------
+
+// The merge of the splits alone, for attn_decode_fp8.hip, whose partials
+// have this file's form (attn_cache.h).
+void fa_decode_combine(const float* o_part, const float* lse_part, void* out,
+                       float* lse, int n_splits, long BH, int head_dim,
+                       hipStream_t stream) {
+  if (head_dim == 64)
+    hipLaunchKernelGGL(fa_decode_combine_kernel<64>, dim3((unsigned)BH),
+                       dim3(64), 0, stream, o_part, lse_part, (__bf16*)out,
+                       lse, n_splits);
+  else
+    hipLaunchKernelGGL(fa_decode_combine_kernel<128>, dim3((unsigned)BH),
+                       dim3(64), 0, stream, o_part, lse_part, (__bf16*)out,
+                       lse, n_splits);
+}
 
 // The split count the policy (num_splits <= 0) or the caller (>= 1) gets for
 // these shapes on `device` (the tensors' device index): the size of the

@@ -130,6 +130,21 @@ void fa_decode(const void* q, void* k_cache, void* v_cache,
                float scale, int n_splits, const int* block_table,
                int n_pages, int page_size, int max_pages, int device,
                hipStream_t stream);
+void fa_decode_fp8(const void* q, void* k_cache, void* v_cache,
+                   const int* seqlens, const void* k_new, const void* v_new,
+                   const float* k_scale, const float* v_scale, void* out,
+                   float* lse, float* o_part, float* lse_part, int B, int H,
+                   int Hk, int Smax, int head_dim, const long* strides,
+                   float scale, int n_splits, const int* block_table,
+                   int n_pages, int page_size, int max_pages, int device,
+                   hipStream_t stream);
+void fa_kv_append(void* k_cache, void* v_cache, const void* k_new,
+                  const void* v_new, const int* seqlens, const int* q_lens,
+                  const float* k_scale, const float* v_scale,
+                  const long* cache_strides, const long* new_strides, int B,
+                  int Hk, int Sq, int Smax, int head_dim,
+                  const int* block_table, int n_pages, int page_size,
+                  int max_pages, int device, hipStream_t stream);
 void fa_extend(const void* q, void* k_cache, void* v_cache,
                const int* seqlens, const int* q_lens, const void* k_new,
                const void* v_new, void* out, float* lse, int B, int H, int Hk,
@@ -458,6 +473,73 @@ PYBIND11_MODULE(_core, m) {
         py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0,
         py::arg("block_table") = 0, py::arg("n_pages") = 0,
         py::arg("page_size") = 0, py::arg("max_pages") = 0);
+  // Decode over e4m3 caches (attn_decode_fp8.hip): fa_decode's arguments,
+  // the cache strides in bytes, plus k_scale and v_scale, fp32 [Hk] on the
+  // device. q, out, k_new and v_new stay bf16; new rows are quantised as
+  // they are appended.
+  m.def("fa_decode_fp8",
+        [](uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+           uintptr_t seqlens, uintptr_t k_scale, uintptr_t v_scale,
+           uintptr_t out, int B, int H, int Hk, int Smax, int head_dim,
+           const std::vector<long>& strides, float scale, int n_splits,
+           int device, uintptr_t stream, uintptr_t k_new, uintptr_t v_new,
+           uintptr_t lse, uintptr_t o_part, uintptr_t lse_part,
+           uintptr_t block_table, int n_pages, int page_size,
+           int max_pages) {
+          if (strides.size() != 12)
+            throw std::runtime_error("fa_decode_fp8: need 12 strides");
+          adapcc::fa_decode_fp8(
+              (const void*)q, (void*)k_cache, (void*)v_cache,
+              (const int*)seqlens, (const void*)k_new, (const void*)v_new,
+              (const float*)k_scale, (const float*)v_scale, (void*)out,
+              (float*)lse, (float*)o_part, (float*)lse_part, B, H, Hk, Smax,
+              head_dim, strides.data(), scale, n_splits,
+              (const int*)block_table, n_pages, page_size, max_pages, device,
+              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seqlens"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("out"), py::arg("B"), py::arg("H"), py::arg("Hk"),
+        py::arg("Smax"), py::arg("head_dim"), py::arg("strides"),
+        py::arg("scale"), py::arg("n_splits"), py::arg("device"),
+        py::arg("stream"), py::arg("k_new") = 0, py::arg("v_new") = 0,
+        py::arg("lse") = 0, py::arg("o_part") = 0, py::arg("lse_part") = 0,
+        py::arg("block_table") = 0, py::arg("n_pages") = 0,
+        py::arg("page_size") = 0, py::arg("max_pages") = 0);
+  // The append step alone (attn_decode_fp8.hip): bf16 rows k_new, v_new
+  // [B,Hk,Sq,head_dim] to cache rows seqlens[b] + i, i < n_b. k_scale and
+  // v_scale != 0: e4m3 caches, rows quantised; both 0: bf16 caches.
+  // cache_strides, new_strides: k then v, (b, h, row) each.
+  m.def("fa_kv_append",
+        [](uintptr_t k_cache, uintptr_t v_cache, uintptr_t k_new,
+           uintptr_t v_new, uintptr_t seqlens, int B, int Hk, int Sq,
+           int Smax, int head_dim, const std::vector<long>& cache_strides,
+           const std::vector<long>& new_strides, int device,
+           uintptr_t stream, uintptr_t q_lens, uintptr_t k_scale,
+           uintptr_t v_scale, uintptr_t block_table, int n_pages,
+           int page_size, int max_pages) {
+          if (cache_strides.size() != 6 || new_strides.size() != 6)
+            throw std::runtime_error("fa_kv_append: need 6 + 6 strides");
+          adapcc::fa_kv_append(
+              (void*)k_cache, (void*)v_cache, (const void*)k_new,
+              (const void*)v_new, (const int*)seqlens, (const int*)q_lens,
+              (const float*)k_scale, (const float*)v_scale,
+              cache_strides.data(), new_strides.data(), B, Hk, Sq, Smax,
+              head_dim, (const int*)block_table, n_pages, page_size,
+              max_pages, device, reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new"),
+        py::arg("v_new"), py::arg("seqlens"), py::arg("B"), py::arg("Hk"),
+        py::arg("Sq"), py::arg("Smax"), py::arg("head_dim"),
+        py::arg("cache_strides"), py::arg("new_strides"), py::arg("device"),
+        py::arg("stream"), py::arg("q_lens") = 0, py::arg("k_scale") = 0,
+        py::arg("v_scale") = 0, py::arg("block_table") = 0,
+        py::arg("n_pages") = 0, py::arg("page_size") = 0,
+        py::arg("max_pages") = 0);
   // Multi-row attention over a KV cache (attn_extend.hip). q and out
   // [B,H,Sq,head_dim], caches [B,Hk,Smax,head_dim], seqlens int32 [B] on the
   // device, q_lens int32 [B] or 0, lse fp32 [B,H,Sq] or 0. strides: q,

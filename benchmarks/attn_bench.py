@@ -31,7 +31,9 @@ with enable_gqa and against this project's flash_attention(causal=False) on
 the one-row query (which, its kernels being self-attention only, resolves to
 SDPA without a mask on the cache cut to the common length), and prints microseconds and the K/V bytes per second,
 2 * B * Hk * len * D * 2 bytes over the time. --sweep adds forced split
-counts, the measurement behind the split policy's constants.
+counts, the measurement behind the split policy's constants. --fp8 (decode
+only) instead times the e4m3 cache of the same keys against the bf16 one,
+and with --page-size both through a block table as well.
 extend: a block of Sq query rows per sequence over a KV cache, causal, with
 the same heads as decode: pure prefill (B8, Sq 1024 and 1000, empty cache),
 chunked prefill (B8, Sq 512 over 3584 cached keys) and short chunks (B32 and
@@ -102,8 +104,15 @@ def main():
                     help="decode and extend: time a paged cache of this page "
                          "size (a power of two >= 16) against the contiguous "
                          "one instead")
+    ap.add_argument("--fp8", action="store_true",
+                    help="decode: time an e4m3 KV cache against the bf16 one "
+                         "(with --page-size also both paged)")
     args = ap.parse_args()
     drop = args.dropout
+    if args.fp8:
+        if args.shape != "decode":
+            ap.error("--fp8 goes with --shape decode")
+        return fp8_path(args.head_dim, args.kv_heads, args.page_size)
     if args.page_size:
         if args.shape not in ("decode", "extend"):
             ap.error("--page-size goes with --shape decode or extend")
@@ -259,6 +268,79 @@ def decode_path(D, kv_heads, sweep):
                           f"{nbytes / ms / 1e9:6.2f} TB/s  "
                           f"this/decode {ms / base:.2f}")
                 del q, k, v, mask, ref
+
+
+def fp8_path(D, kv_heads, P):
+    """--fp8: decode over an e4m3 cache against the bf16 cache of the same
+    keys, alternating in one process, at decode_path's shapes; with
+    --page-size also both through a block table. 'bf16 again' is the first
+    candidate a second time: what two timings of one code differ by. Bytes
+    per second count the K/V bytes of the candidate's own cache; the bound on
+    fp8 / bf16 time is the byte ratio, 0.5."""
+    from adapcc_amd.ops.attention import (fa_decode_supported,
+                                          flash_attention_decode,
+                                          kv_quantize_reference)
+
+    H = 16 if D == 128 else 12
+    kv = [kv_heads] if kv_heads else ([16, 4, 1] if D == 128 else [12, 1])
+    for B in (1, 32):
+        for Hk in kv:
+            for n in (1024, 16384):
+                torch.manual_seed(0)
+                q = torch.randn(B, H, D, device="cuda", dtype=torch.bfloat16)
+                k = torch.randn(B, Hk, n, D, device="cuda",
+                                dtype=torch.bfloat16)
+                v = torch.randn_like(k)
+                lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                ks = torch.full((Hk,), 6.0 / 448, device="cuda")
+                vs = ks.clone()
+                k8 = kv_quantize_reference(k, ks)
+                v8 = kv_quantize_reference(v, vs)
+                sc = dict(k_scale=ks, v_scale=vs)
+                # a missing kernel is an error, not a composed-route run
+                assert fa_decode_supported(q, k, v, lens)
+                assert fa_decode_supported(q, k8, v8, lens, **sc)
+                fns = {
+                    "bf16": lambda: flash_attention_decode(q, k, v, lens),
+                    "fp8": lambda: flash_attention_decode(q, k8, v8, lens,
+                                                          **sc),
+                    "bf16 again": lambda: flash_attention_decode(q, k, v,
+                                                                 lens),
+                }
+                if P:
+                    mp = n // P
+                    table = torch.randperm(B * mp, device="cuda").view(B, mp)
+                    pools = []
+                    for t in (k, v, k8.view(torch.uint8), v8.view(torch.uint8)):
+                        pool = torch.empty(B * mp, Hk, P, D, device="cuda",
+                                           dtype=t.dtype)
+                        pool[table.view(-1)] = t.view(
+                            B, Hk, mp, P, D).transpose(1, 2).reshape(
+                                -1, Hk, P, D)
+                        pools.append(pool)
+                    kp, vp = pools[:2]
+                    kp8, vp8 = (t.view(k8.dtype) for t in pools[2:])
+                    table = table.int()
+                    assert fa_decode_supported(q, kp8, vp8, lens, table, **sc)
+                    fns[f"bf16 paged P={P}"] = lambda: flash_attention_decode(
+                        q, kp, vp, lens, block_table=table)
+                    fns[f"fp8 paged P={P}"] = lambda: flash_attention_decode(
+                        q, kp8, vp8, lens, block_table=table, **sc)
+                err = (flash_attention_decode(q, k8, v8, lens, **sc).float()
+                       - flash_attention_decode(q, k, v, lens).float()
+                       ).abs().max().item()
+                nbytes = 2 * B * Hk * n * D * 2
+                print(f"B{B} H{H} Hk{Hk} D{D} len{n}  (bf16 K/V "
+                      f"{nbytes / 2**20:.1f} MiB, max |fp8 - bf16| {err:.2e})")
+                base = None
+                for name, (ms, lo, hi) in alternate(fns, window=0.3).items():
+                    base = base or ms
+                    nb = nbytes // 2 if name.startswith("fp8") else nbytes
+                    print(f"  {name:<22} {ms * 1e3:9.1f} us  (rounds "
+                          f"{lo * 1e3:.1f}..{hi * 1e3:.1f})  "
+                          f"{nb / ms / 1e9:6.2f} TB/s  "
+                          f"this/bf16 {ms / base:.3f}")
+                del q, k, v, k8, v8, fns
 
 
 def paged_path(shape, P):
