@@ -78,7 +78,9 @@ class CausalSelfAttention(nn.Module):
         is the decode step, ``flash_attention_decode``. With ``table``
         (int32 [B,max_pages]) and ``page`` the cache is paged: ``k``, ``v``
         are pools [B * max_pages, page, Hk, D] and both calls get the table
-        as ``block_table``."""
+        as ``block_table``. With ``dtype`` (``torch.float8_e4m3fn``) the
+        cache is made of that dtype and both calls get ``k_scale`` and
+        ``v_scale`` (fp32 [Hk]) from the dict."""
         from ..ops import attention
 
         H, Hk = self.n_head, self.n_kv_head
@@ -87,18 +89,20 @@ class CausalSelfAttention(nn.Module):
         D = W // (H + 2 * Hk)
         q, k, v = qkv.split([H * D, Hk * D, Hk * D], dim=-1)
         table = cache.get("table")
+        scales = {n: cache[n] for n in ("k_scale", "v_scale") if n in cache}
         if T == 1 and "k" in cache and cache.get("q_lens") is None:
             y = attention.flash_attention_decode(
                 q.view(B, H, D), cache["k"].transpose(1, 2),
                 cache["v"].transpose(1, 2), cache["lens"],
                 k_new=k.view(B, Hk, D), v_new=v.view(B, Hk, D),
-                block_table=table)
+                block_table=table, **scales)
             return self.c_proj(y.view(B, 1, H * D))
         if "k" not in cache:
             shape = ((B, cache["Smax"]) if table is None
                      else (table.numel(), cache["page"]))
-            cache["k"] = qkv.new_empty(*shape, Hk, D)
-            cache["v"] = qkv.new_empty(*shape, Hk, D)
+            dtype = cache.get("dtype", qkv.dtype)
+            cache["k"] = qkv.new_empty(*shape, Hk, D, dtype=dtype)
+            cache["v"] = qkv.new_empty(*shape, Hk, D, dtype=dtype)
         lens = cache.get("lens")
         if lens is None:
             lens = torch.zeros(B, dtype=torch.int32, device=x.device)
@@ -107,7 +111,7 @@ class CausalSelfAttention(nn.Module):
             cache["v"].transpose(1, 2), lens,
             k_new=k.view(B, T, Hk, D).transpose(1, 2),
             v_new=v.view(B, T, Hk, D).transpose(1, 2),
-            q_lens=cache.get("q_lens"), block_table=table)
+            q_lens=cache.get("q_lens"), block_table=table, **scales)
         return self.c_proj(y.transpose(1, 2).view(B, T, H * D))
 
     def forward(self, x: torch.Tensor,
@@ -286,7 +290,9 @@ class GPT2(nn.Module):
                  return_logits: bool = False,
                  prompt_lens: torch.Tensor = None,
                  prefill_chunk: int = None,
-                 kv_page_size: int = None):
+                 kv_page_size: int = None,
+                 kv_cache_dtype: torch.dtype = None,
+                 kv_scales=None):
         """Greedy continuation of the prompts idx [B,T], T + max_new_tokens
         <= n_positions: returns [B, T + max_new_tokens], and with
         ``return_logits`` also the [B, max_new_tokens, vocab] logits each
@@ -315,7 +321,17 @@ class GPT2(nn.Module):
         hands the pages out interleaved across the sequences (page j of
         sequence b is pool page j * B + b), which every prefill chunk and
         decode step passes as ``block_table``. The tokens are the unpaged
-        run's."""
+        run's.
+
+        ``kv_cache_dtype=torch.float8_e4m3fn`` stores every layer's caches
+        (or pools) as e4m3, half the bytes: rows are quantised as they are
+        appended and every chunk and step attends over the stored codes, so
+        chunking, raggedness and paging change nothing about what is
+        attended. ``kv_scales`` is an optional pair (k, v) of fp32
+        [n_layer, Hk] tensors on idx's device, a stored byte c of layer l,
+        head hk standing for float(c) * scale[l, hk]; the default is ones.
+        None keeps the caches in the model's dtype; any other dtype
+        raises."""
         B, T = idx.shape
         total = T + max_new_tokens
         if T < 1 or max_new_tokens < 1 or total > self.cfg.n_positions:
@@ -338,6 +354,29 @@ class GPT2(nn.Module):
             plens = torch.full((B,), T, dtype=torch.int32, device=idx.device)
         batch = torch.arange(B, device=idx.device)
         caches = [{"Smax": total} for _ in self.h]
+        if kv_cache_dtype is not None:
+            if kv_cache_dtype != torch.float8_e4m3fn:
+                raise ValueError("GPT2.generate: kv_cache_dtype must be None "
+                                 "or torch.float8_e4m3fn, got "
+                                 f"{kv_cache_dtype}")
+            Hk = self.h[0].attn.n_kv_head
+            if kv_scales is None:
+                kv_scales = (torch.ones(len(self.h), Hk, device=idx.device),
+                             ) * 2
+            ks, vs = kv_scales
+            for s in (ks, vs):
+                if (s.dtype != torch.float32 or s.shape != (len(self.h), Hk)
+                        or s.device != idx.device):
+                    raise ValueError("GPT2.generate: kv_scales must be two "
+                                     f"fp32 [{len(self.h)},{Hk}] tensors on "
+                                     "idx's device")
+            for i, cache in enumerate(caches):
+                cache.update(dtype=kv_cache_dtype,
+                             k_scale=ks[i].contiguous(),
+                             v_scale=vs[i].contiguous())
+        elif kv_scales is not None:
+            raise ValueError("GPT2.generate: kv_scales goes with "
+                             "kv_cache_dtype=torch.float8_e4m3fn")
         if kv_page_size is not None:
             P = int(kv_page_size)
             if P < 1:

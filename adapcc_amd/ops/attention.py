@@ -94,8 +94,13 @@ the bf16 MFMA path, and fold the scales into the softmax scale and the final
 normalisation; q, the new rows and the output stay bf16. Rows are quantised
 when they are written, by one function, ``kv_quantize_reference``
 (divide, clamp to +-448, round to nearest even): by decode's own append and
-by ``kv_cache_append``, the append step alone, which is how a bf16 prefill
-fills such a cache. ``flash_attention_extend`` does not take e4m3 caches.
+by ``kv_cache_append``, the append step alone, which is one way a prompt
+enters such a cache. ``flash_attention_extend`` takes the same caches and
+scales (csrc/attn_extend_fp8.hip: the bytes are converted once per workgroup
+on their way into LDS, and the bf16 kernel's tiles, MFMAs and split merge do
+the rest): chunked prefill, a further turn and drafted tokens run on the e4m3
+cache itself. It quantises a chunk's rows first and attends over them as
+stored, so a prompt sees the same keys however it is chunked.
 """
 
 from __future__ import annotations
@@ -743,8 +748,8 @@ def _check_cached(name, q, k_cache, v_cache, cache_seqlens, k_new, v_new,
     """The argument checks of the calls over a KV cache. q is [B,H,D]
     (decode) or [B,H,Sq,D] (extend), new rows then [B,Hk,D] or [B,Hk,Sq,D];
     q_lens (extend) like cache_seqlens. With block_table (int32
-    [B,max_pages]) the caches are page pools [N,Hk,P,D]. fp8_ok (decode and
-    ``kv_cache_append``): e4m3 caches under a q of another float dtype are
+    [B,max_pages]) the caches are page pools [N,Hk,P,D]. fp8_ok (decode, extend
+    and ``kv_cache_append``): e4m3 caches under a q of another float dtype are
     taken, with k_scale and v_scale, fp32 [Hk]."""
     rows = "" if name.endswith("decode") else "Sq,"
     paged = block_table is not None
@@ -1016,9 +1021,11 @@ def kv_cache_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
     modified nor read on the host. Caches of k_new's dtype take the rows as
     they are; e4m3 caches (``torch.float8_e4m3fn``) need ``k_scale`` and
     ``v_scale`` (fp32 [Hk]) and take ``kv_quantize_reference`` of them, so a
-    stored byte c of head hk stands for float(c) * scale[hk]. This is how a
-    prompt enters an e4m3 cache: prefill attention runs in bf16, its k and v
-    are appended here, and ``flash_attention_decode`` then steps over e4m3.
+    stored byte c of head hk stands for float(c) * scale[hk]. This is one way
+    a prompt enters an e4m3 cache: prefill attention runs in bf16, its k and
+    v are appended here, and ``flash_attention_decode`` then steps over e4m3
+    (``flash_attention_extend`` with the scales is the other: it appends
+    first and attends over the stored rows).
     bf16 rows on the GPU run the append kernels (csrc/attn_extend.hip,
     csrc/attn_decode_fp8.hip); anything else is composed in torch."""
     name = "kv_cache_append"
@@ -1053,24 +1060,34 @@ def kv_cache_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
                      block_table)
 
 
-def _fp8_decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
-                         scale, return_lse, block_table, k_scale, v_scale):
-    """Decode over e4m3 caches off the kernel path, and its definition: the
+def _fp8_extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                         q_lens, causal, scale, return_lse, block_table,
+                         k_scale, v_scale):
+    """Extend over e4m3 caches off the kernel path, and its definition: the
     new rows quantised and written, the caches dequantised to q's dtype,
     then the composed route on those with no new rows and the lengths
     advanced on the device."""
     lens = cache_seqlens
     if k_new is not None:
-        _append_composed(
-            k_cache, v_cache, cache_seqlens,
-            kv_quantize_reference(k_new.unsqueeze(2), k_scale),
-            kv_quantize_reference(v_new.unsqueeze(2), v_scale), None,
-            block_table)
-        lens = cache_seqlens.clamp(min=0) + 1     # clamped to Smax below
+        _append_composed(k_cache, v_cache, cache_seqlens,
+                         kv_quantize_reference(k_new, k_scale),
+                         kv_quantize_reference(v_new, v_scale), q_lens,
+                         block_table)
+        n = q.shape[2] if q_lens is None else q_lens.clamp(0, q.shape[2])
+        lens = cache_seqlens.clamp(min=0) + n     # clamped to Smax below
     kd, vd = ((c.float() * s.view(1, -1, 1, 1)).to(q.dtype)
               for c, s in ((k_cache, k_scale), (v_cache, v_scale)))
-    res = _extend_composed(q.unsqueeze(2), kd, vd, lens, None, None, None,
-                           True, scale, return_lse, block_table)
+    return _extend_composed(q, kd, vd, lens, None, None, q_lens, causal,
+                            scale, return_lse, block_table)
+
+
+def _fp8_decode_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                         scale, return_lse, block_table, k_scale, v_scale):
+    """Decode over e4m3 caches off the kernel path: a block of one row."""
+    one = [None if t is None else t.unsqueeze(2) for t in (q, k_new, v_new)]
+    res = _fp8_extend_composed(one[0], k_cache, v_cache, cache_seqlens,
+                               one[1], one[2], None, True, scale, return_lse,
+                               block_table, k_scale, v_scale)
     return (res[0][:, :, 0], res[1][:, :, 0]) if return_lse else res[:, :, 0]
 
 
@@ -1155,14 +1172,18 @@ def flash_attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
 def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
                         v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
                         q_lens: Optional[torch.Tensor] = None,
-                        block_table: Optional[torch.Tensor] = None) -> bool:
-    """True where ``flash_attention_extend`` runs its kernels: bf16 on the
+                        block_table: Optional[torch.Tensor] = None,
+                        k_scale: Optional[torch.Tensor] = None,
+                        v_scale: Optional[torch.Tensor] = None) -> bool:
+    """True where ``flash_attention_extend`` runs its kernels: bf16 q on the
     GPU, head_dim 64 or 128, at most 32 query heads per K/V head, rows
     contiguous and 16-B aligned, extension built; with ``block_table`` also
-    a page size that is a power of two >= 16 and a contiguous table."""
+    a page size that is a power of two >= 16 and a contiguous table. The
+    caches are bf16, or e4m3 with ``k_scale`` and ``v_scale``."""
     try:
         _check_cached("flash_attention_extend", q, k_cache, v_cache,
-                      cache_seqlens, None, None, q_lens, block_table)
+                      cache_seqlens, None, None, q_lens, block_table, k_scale,
+                      v_scale, fp8_ok=True)
     except ValueError:
         return False
     return _cached_kernel_ok(q, k_cache, v_cache, cache_seqlens, q_lens,
@@ -1171,9 +1192,10 @@ def fa_extend_supported(q: torch.Tensor, k_cache: torch.Tensor,
 
 def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
                    causal, scale, return_lse, num_splits=None,
-                   block_table=None):
+                   block_table=None, k_scale=None, v_scale=None):
     """The kernel path, for arguments that passed ``_check_cached`` and
-    ``_cached_kernel_ok``."""
+    ``_cached_kernel_ok``. With the scales: e4m3 caches and the kernels of
+    csrc/attn_extend_fp8.hip."""
     core = _core()
     B, H, Sq, D = q.shape
     Hk = k_cache.shape[1]
@@ -1196,10 +1218,17 @@ def _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new, v_new, q_lens,
         a.kw.update(q_lens=q_lens.data_ptr())
     strides = (_strides3(q) + _strides3(k_cache) + _strides3(v_cache)
                + _strides3(out) + a.new_strides)
-    core.fa_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                   cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk, Sq,
-                   Smax, D, strides, scale, bool(causal), a.device, a.stream,
-                   **a.kw)
+    if k_scale is not None:
+        core.fa_extend_fp8(q.data_ptr(), k_cache.data_ptr(),
+                           v_cache.data_ptr(), cache_seqlens.data_ptr(),
+                           k_scale.data_ptr(), v_scale.data_ptr(),
+                           out.data_ptr(), B, H, Hk, Sq, Smax, D, strides,
+                           scale, bool(causal), a.device, a.stream, **a.kw)
+    else:
+        core.fa_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                       cache_seqlens.data_ptr(), out.data_ptr(), B, H, Hk,
+                       Sq, Smax, D, strides, scale, bool(causal), a.device,
+                       a.stream, **a.kw)
     return (out, a.lse) if return_lse else out
 
 
@@ -1307,7 +1336,9 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
                            causal: bool = True, scale: float = None,
                            return_lse: bool = False,
                            num_splits: Optional[int] = None,
-                           block_table: Optional[torch.Tensor] = None):
+                           block_table: Optional[torch.Tensor] = None,
+                           k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None):
     """Attention of a block of Sq query rows per sequence over a KV cache:
     chunked prefill, a further turn on a kept cache, a few drafted tokens,
     or (non-causal, no new rows) cross-attention. q: [B,H,Sq,D]; k_cache,
@@ -1359,9 +1390,28 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
     of two >= 16 and a contiguous table, and give the output bits of the
     unpaged call on the gathered slab of the same Smax and split count;
     anything else gathers the pages, composes as above and writes the
-    appended rows back."""
+    appended rows back.
+
+    FP8 cache: k_cache and v_cache of dtype ``torch.float8_e4m3fn`` (slabs
+    or pools, rows 16-B aligned: leading strides multiples of 16) with
+    ``k_scale`` and ``v_scale``, fp32 [Hk] on the same device, positive: a
+    stored byte c of K/V head hk stands for float(c) * scale[hk]. q, k_new,
+    v_new and the output keep q's dtype, and lse is the logsumexp of the
+    scaled scores of the dequantised keys. The scales are read on the device
+    only. New rows are stored as ``kv_quantize_reference`` of them before
+    the attention, which reads them back as stored: the chunk attends over
+    its own quantised keys, so a prompt gives the same attention inputs
+    however it is cut into chunks. That differs from a bf16 prefill followed
+    by ``kv_cache_append``, where the prompt attends over the unquantised
+    keys and only later tokens see the stored ones. bf16 q runs the kernels
+    of csrc/attn_extend_fp8.hip, which read half the bytes, convert them
+    once per workgroup on the way into LDS (e4m3 -> bf16 is exact) and fold
+    the scales into the softmax scale and the final normalisation; anything
+    else quantises and writes the new rows, dequantises the caches to q's
+    dtype and composes as above."""
     _check_cached("flash_attention_extend", q, k_cache, v_cache,
-                  cache_seqlens, k_new, v_new, q_lens, block_table)
+                  cache_seqlens, k_new, v_new, q_lens, block_table, k_scale,
+                  v_scale, fp8_ok=True)
     _check_no_grad("flash_attention_extend", q, k_cache, v_cache, k_new,
                    v_new)
     if num_splits is not None and int(num_splits) < 1:
@@ -1372,6 +1422,10 @@ def flash_attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
         s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _launch_extend(q, k_cache, v_cache, cache_seqlens, k_new,
                               v_new, q_lens, causal, s, return_lse,
-                              num_splits, block_table)
+                              num_splits, block_table, k_scale, v_scale)
+    if k_scale is not None:
+        return _fp8_extend_composed(q, k_cache, v_cache, cache_seqlens, k_new,
+                                    v_new, q_lens, causal, scale, return_lse,
+                                    block_table, k_scale, v_scale)
     return _extend_composed(q, k_cache, v_cache, cache_seqlens, k_new, v_new,
                             q_lens, causal, scale, return_lse, block_table)

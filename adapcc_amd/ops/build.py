@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # adapcc_
 CSRC = os.path.join(PKG_DIR, "ops", "csrc")
 SOURCES = ["kernels.hip", "engine.hip", "plan.cpp", "lnorm.hip", "ce.hip",
            "attn.hip", "attn_probe.hip", "attn_decode.hip", "attn_extend.hip",
-           "attn_decode_fp8.hip", "gelu.hip",
+           "attn_decode_fp8.hip", "attn_extend_fp8.hip", "gelu.hip",
            "moe.hip", "colsum.hip", "bindings.hip"]
 HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h", "attn_drop.h",
            "ln_cols.h", "attn_decode_plan.h", "attn_cache.h"]
@@ -31,7 +31,8 @@ HEADERS = ["common.h", "engine.h", "plan.h", "attn_frag.h", "attn_drop.h",
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"attn_decode.hip": NO_PACKED_FP32,
                "attn_extend.hip": NO_PACKED_FP32,
-               "attn_decode_fp8.hip": NO_PACKED_FP32}
+               "attn_decode_fp8.hip": NO_PACKED_FP32,
+               "attn_extend_fp8.hip": NO_PACKED_FP32}
 OUT_SO = os.path.join(PKG_DIR, "_core.so")
 STAMP = os.path.join(PKG_DIR, "ops", ".build_stamp")
 

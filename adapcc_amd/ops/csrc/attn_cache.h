@@ -10,9 +10,11 @@
 // a function call it got another register allocation and lost time at one
 // shape (profiles/README.md, "Shared header ..."). attn_decode_fp8.hip, decode
 // over an e4m3 cache, is a third user: the lengths, the page map, the tile
-// step, and decode's combine kernel through a host launcher. Compiled only
-// through these files, so with their flags (ops/build.py: packed fp32 VALU
-// forms off).
+// step, and decode's combine kernel through a host launcher.
+// attn_extend_fp8.hip, extend over an e4m3 cache, is a fourth: all of that
+// with extend's combine kernel, and cvt8, the e4m3 -> bf16 conversion both
+// fp8 files use. Compiled only through these files, so with their flags
+// (ops/build.py: packed fp32 VALU forms off).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -124,6 +126,22 @@ __device__ __forceinline__ void store4_bf16(__bf16* dst, float a, float b,
   *reinterpret_cast<uint2*>(dst) = st;
 }
 
+// Eight e4m3 codes (two dwords, byte 0 first) -> eight bf16, exactly:
+// v_cvt_scalef32_pk_bf16_fp8 at scale 1.0, one instruction per two codes.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+
+__device__ __forceinline__ bf16x8 cvt8(unsigned a, unsigned b) {
+  union {
+    bf16x2 h[4];
+    bf16x8 f;
+  } r;
+  r.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false);
+  r.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true);
+  r.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false);
+  r.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true);
+  return r.f;
+}
+
 // One 32-key tile of the online softmax and of O^T += V^T · P^T. `s` is the
 // finished S^T tile (this lane: keys kbase + crow(r, lane >> 5) of its own
 // row). `masked` is wave-uniform: the tile reaches past some lane's `lim`,
@@ -231,6 +249,15 @@ void fa_cache_append_fp8(void* k_cache, void* v_cache, const void* k_new,
 // [BH, n_splits] to out bf16 [BH, head_dim] and lse fp32 [BH] (or null).
 void fa_decode_combine(const float* o_part, const float* lse_part, void* out,
                        float* lse, int n_splits, long BH, int head_dim,
+                       hipStream_t stream);
+
+// Extend's merge of the key splits (attn_extend.hip's combine kernel): o_part
+// fp32 [B, H, Sq, n_splits, head_dim] normalised partials and lse_part fp32
+// [B, H, Sq, n_splits] to out bf16 through its (b, h, row) element strides
+// and lse fp32 [B, H, Sq] (or null).
+void fa_extend_combine(const float* o_part, const float* lse_part, void* out,
+                       float* lse, int B, int H, int Sq, int n_splits,
+                       int head_dim, long o_sb, long o_sh, long o_ss,
                        hipStream_t stream);
 
 // The PageMap of a host call, checked (attn_decode_plan.h): block_table null

@@ -34,8 +34,9 @@
 //    converted in registers and written as two 16-B slots of the wave's
 //    [32][64] bf16 row image(s) (attn_frag.h), so ds_read_b64_tr_b16, the
 //    PV MFMAs and the LDS budget are the bf16 kernel's.
-//  * Conversion: v_cvt_scalef32_pk_bf16_fp8 with scale 1.0, one instruction
-//    per two codes straight to a packed bf16 pair (8 per 16-B load). The
+//  * Conversion (attn_cache.h's cvt8): v_cvt_scalef32_pk_bf16_fp8 with
+//    scale 1.0, one instruction per two codes straight to a packed bf16 pair
+//    (8 per 16-B load). The
 //    alternative, v_cvt_pk_f32_fp8 then v_cvt_pk_bf16_f32, is two per pair;
 //    chosen by that count, the alternative was not timed.
 //  * Prefetch as in the bf16 kernel: the next sub-tile's raw bytes (D/4
@@ -90,7 +91,6 @@ namespace {
 constexpr int kBlkImg = 4096;  // attn_frag.h's [32][64] bf16 row image
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 struct DecodeFp8Params {
   const __bf16* q;
@@ -108,19 +108,6 @@ struct DecodeFp8Params {
   float* lse;               // [B, H], may be null
   PageMap pg;               // kPaged: k, v are pools, k_sb, v_sb page strides
 };
-
-// Eight e4m3 codes (two dwords, byte 0 first) -> eight bf16, exactly.
-__device__ __forceinline__ bf16x8 cvt8(unsigned a, unsigned b) {
-  union {
-    bf16x2 h[4];
-    bf16x8 f;
-  } r;
-  r.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false);
-  r.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true);
-  r.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false);
-  r.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true);
-  return r.f;
-}
 
 // A lane's raw bytes of one sub-tile of K or of V: kHD/32 loads of 16 B.
 template <int kHD>

@@ -679,6 +679,24 @@ void fa_cache_append(void* k_cache, void* v_cache, const void* k_new,
                        stream, a);
 }
 
+// attn_cache.h describes the arguments: the launch of launch_extend's second
+// step, for attn_extend_fp8.hip.
+void fa_extend_combine(const float* o_part, const float* lse_part, void* out,
+                       float* lse, int B, int H, int Sq, int n_splits,
+                       int head_dim, long o_sb, long o_sh, long o_ss,
+                       hipStream_t stream) {
+  const long rows = (long)B * H * Sq;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (head_dim == 64)
+    hipLaunchKernelGGL(fa_extend_combine_kernel<64>, grid, dim3(256), 0,
+                       stream, o_part, lse_part, (__bf16*)out, lse, rows, H,
+                       Sq, n_splits, o_sb, o_sh, o_ss);
+  else
+    hipLaunchKernelGGL(fa_extend_combine_kernel<128>, grid, dim3(256), 0,
+                       stream, o_part, lse_part, (__bf16*)out, lse, rows, H,
+                       Sq, n_splits, o_sb, o_sh, o_ss);
+}
+
 // The split count the policy (num_splits <= 0) or the caller (>= 1) gets for
 // these shapes (G = H / Hk) on `device`, the tensors' device index: the size
 // of the o_part / lse_part workspaces.

@@ -154,6 +154,15 @@ void fa_extend(const void* q, void* k_cache, void* v_cache,
                int page_size, int max_pages, int device, hipStream_t stream);
 int fa_extend_splits(int B, int Hk, int Sq, int G, int Smax, int num_splits,
                      int device);
+void fa_extend_fp8(const void* q, void* k_cache, void* v_cache,
+                   const int* seqlens, const int* q_lens, const void* k_new,
+                   const void* v_new, const float* k_scale,
+                   const float* v_scale, void* out, float* lse, int B, int H,
+                   int Hk, int Sq, int Smax, int head_dim, const long* strides,
+                   float scale, bool causal, int n_splits, float* o_part,
+                   float* lse_part, const int* block_table, int n_pages,
+                   int page_size, int max_pages, int device,
+                   hipStream_t stream);
 void mfma_probe(const void* a, const void* b, float* c, hipStream_t stream);
 void gelu_forward(int dtype, const void* x, void* y, long n,
                   hipStream_t stream);
@@ -578,6 +587,44 @@ PYBIND11_MODULE(_core, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("seqlens"), py::arg("out"), py::arg("B"), py::arg("H"),
         py::arg("Hk"), py::arg("Sq"), py::arg("Smax"), py::arg("head_dim"),
+        py::arg("strides"), py::arg("scale"), py::arg("causal"),
+        py::arg("device"), py::arg("stream"), py::arg("q_lens") = 0,
+        py::arg("k_new") = 0, py::arg("v_new") = 0, py::arg("lse") = 0,
+        py::arg("n_splits") = 1, py::arg("o_part") = 0,
+        py::arg("lse_part") = 0, py::arg("block_table") = 0,
+        py::arg("n_pages") = 0, py::arg("page_size") = 0,
+        py::arg("max_pages") = 0);
+  // fa_extend over e4m3 caches (attn_extend_fp8.hip): its arguments, the
+  // cache strides in bytes, plus k_scale and v_scale, fp32 [Hk] on the
+  // device. q, out, k_new and v_new stay bf16; new rows are quantised as
+  // they are appended and attended as stored.
+  m.def("fa_extend_fp8",
+        [](uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+           uintptr_t seqlens, uintptr_t k_scale, uintptr_t v_scale,
+           uintptr_t out, int B, int H, int Hk, int Sq, int Smax,
+           int head_dim, const std::vector<long>& strides, float scale,
+           bool causal, int device, uintptr_t stream, uintptr_t q_lens,
+           uintptr_t k_new, uintptr_t v_new, uintptr_t lse, int n_splits,
+           uintptr_t o_part, uintptr_t lse_part, uintptr_t block_table,
+           int n_pages, int page_size, int max_pages) {
+          if (strides.size() != 18)
+            throw std::runtime_error("fa_extend_fp8: need 18 strides");
+          adapcc::fa_extend_fp8(
+              (const void*)q, (void*)k_cache, (void*)v_cache,
+              (const int*)seqlens, (const int*)q_lens, (const void*)k_new,
+              (const void*)v_new, (const float*)k_scale,
+              (const float*)v_scale, (void*)out, (float*)lse, B, H, Hk, Sq,
+              Smax, head_dim, strides.data(), scale, causal, n_splits,
+              (float*)o_part, (float*)lse_part, (const int*)block_table,
+              n_pages, page_size, max_pages, device,
+              reinterpret_cast<hipStream_t>(stream));
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) throw std::runtime_error(hipGetErrorString(e));
+        },
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("seqlens"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("out"), py::arg("B"), py::arg("H"), py::arg("Hk"),
+        py::arg("Sq"), py::arg("Smax"), py::arg("head_dim"),
         py::arg("strides"), py::arg("scale"), py::arg("causal"),
         py::arg("device"), py::arg("stream"), py::arg("q_lens") = 0,
         py::arg("k_new") = 0, py::arg("v_new") = 0, py::arg("lse") = 0,

@@ -32,8 +32,9 @@ the one-row query (which, its kernels being self-attention only, resolves to
 SDPA without a mask on the cache cut to the common length), and prints microseconds and the K/V bytes per second,
 2 * B * Hk * len * D * 2 bytes over the time. --sweep adds forced split
 counts, the measurement behind the split policy's constants. --fp8 (decode
-only) instead times the e4m3 cache of the same keys against the bf16 one,
-and with --page-size both through a block table as well.
+and extend) instead times the e4m3 cache of the same keys against the bf16
+one, and with --page-size both through a block table as well; for extend at
+three shapes of its split sweep (byte-, split- and compute-bound).
 extend: a block of Sq query rows per sequence over a KV cache, causal, with
 the same heads as decode: pure prefill (B8, Sq 1024 and 1000, empty cache),
 chunked prefill (B8, Sq 512 over 3584 cached keys) and short chunks (B32 and
@@ -105,13 +106,15 @@ def main():
                          "size (a power of two >= 16) against the contiguous "
                          "one instead")
     ap.add_argument("--fp8", action="store_true",
-                    help="decode: time an e4m3 KV cache against the bf16 one "
-                         "(with --page-size also both paged)")
+                    help="decode and extend: time an e4m3 KV cache against "
+                         "the bf16 one (with --page-size also both paged)")
     args = ap.parse_args()
     drop = args.dropout
     if args.fp8:
+        if args.shape == "extend":
+            return fp8_extend_path(args.page_size)
         if args.shape != "decode":
-            ap.error("--fp8 goes with --shape decode")
+            ap.error("--fp8 goes with --shape decode or extend")
         return fp8_path(args.head_dim, args.kv_heads, args.page_size)
     if args.page_size:
         if args.shape not in ("decode", "extend"):
@@ -341,6 +344,80 @@ def fp8_path(D, kv_heads, P):
                           f"{nb / ms / 1e9:6.2f} TB/s  "
                           f"this/bf16 {ms / base:.3f}")
                 del q, k, v, k8, v8, fns
+
+
+def fp8_extend_path(P):
+    """--fp8 --shape extend: flash_attention_extend over an e4m3 cache
+    against the bf16 cache of the same keys, fp8_path's method (alternating
+    in one process, 'bf16 again' the noise figure), at three shapes of the
+    split sweep in attn_extend.hip's header: byte-bound (the bound on fp8 /
+    bf16 time is the byte ratio, 0.5), split- and launch-bound, and
+    compute-bound, where fp8 can only cost its conversion. The cache holds
+    the chunk's keys already; '+ append' has the call write them. With
+    --page-size also both through a block table."""
+    from adapcc_amd.ops.attention import (_core, fa_extend_supported,
+                                          flash_attention_extend,
+                                          kv_quantize_reference)
+
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+    for B, H, Hk, D, Sq, keys in ((32, 16, 16, 128, 8, 16384),
+                                  (1, 16, 4, 128, 8, 16384),
+                                  (8, 12, 12, 64, 512, 3584)):
+        torch.manual_seed(0)
+        q = torch.randn(B, H, Sq, D, **bf)
+        k = torch.randn(B, Hk, keys, D, **bf)
+        v = torch.randn_like(k)
+        lens = torch.full((B,), keys, dtype=torch.int32, device="cuda")
+        lens0 = lens - Sq
+        kn, vn = k[:, :, keys - Sq:].clone(), v[:, :, keys - Sq:].clone()
+        ks = torch.full((Hk,), 6.0 / 448, device="cuda")
+        vs = ks.clone()
+        k8, v8 = kv_quantize_reference(k, ks), kv_quantize_reference(v, vs)
+        sc = dict(k_scale=ks, v_scale=vs)
+        # a missing kernel is an error, not a composed-route run
+        assert fa_extend_supported(q, k, v, lens)
+        assert fa_extend_supported(q, k8, v8, lens, **sc)
+        fns = {
+            "bf16": lambda: flash_attention_extend(q, k, v, lens),
+            "fp8": lambda: flash_attention_extend(q, k8, v8, lens, **sc),
+            "bf16 again": lambda: flash_attention_extend(q, k, v, lens),
+            "bf16 + append": lambda: flash_attention_extend(q, k, v, lens0,
+                                                            kn, vn),
+            "fp8 + append": lambda: flash_attention_extend(q, k8, v8, lens0,
+                                                           kn, vn, **sc),
+        }
+        if P:
+            mp = keys // P
+            table = torch.randperm(B * mp, device="cuda").view(B, mp)
+            pools = []
+            for t in (k, v, k8.view(torch.uint8), v8.view(torch.uint8)):
+                pool = torch.empty(B * mp, Hk, P, D, device="cuda",
+                                   dtype=t.dtype)
+                pool[table.view(-1)] = t.view(B, Hk, mp, P, D).transpose(
+                    1, 2).reshape(-1, Hk, P, D)
+                pools.append(pool)
+            kp, vp = pools[:2]
+            kp8, vp8 = (t.view(k8.dtype) for t in pools[2:])
+            table = table.int()
+            assert fa_extend_supported(q, kp8, vp8, lens, None, table, **sc)
+            fns[f"bf16 paged P={P}"] = lambda: flash_attention_extend(
+                q, kp, vp, lens, block_table=table)
+            fns[f"fp8 paged P={P}"] = lambda: flash_attention_extend(
+                q, kp8, vp8, lens, block_table=table, **sc)
+        err = (fns["fp8"]().float() - fns["bf16"]().float()).abs().max().item()
+        nbytes = 2 * B * Hk * keys * D * 2
+        ns = _core().fa_extend_splits(B, Hk, Sq, H // Hk, keys, 0, 0)
+        print(f"B{B} H{H} Hk{Hk} D{D} Sq{Sq} keys{keys}  (bf16 K/V "
+              f"{nbytes / 2**20:.1f} MiB, {ns} splits, max |fp8 - bf16| "
+              f"{err:.2e})")
+        base = None
+        for name, (ms, lo, hi) in alternate(fns, window=0.5).items():
+            base = base or ms
+            nb = nbytes // 2 if name.startswith("fp8") else nbytes
+            print(f"  {name:<22} {ms * 1e3:9.1f} us  (rounds "
+                  f"{lo * 1e3:.1f}..{hi * 1e3:.1f})  "
+                  f"{nb / ms / 1e9:6.2f} TB/s  this/bf16 {ms / base:.3f}")
+        del q, k, v, k8, v8, fns
 
 
 def paged_path(shape, P):
